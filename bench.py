@@ -11,7 +11,12 @@ tests fire) of the 300-camera / 100k-point / 600k-observation synthetic circle, 
 camera 0 fixed, focal fixed -- the calibrated configuration of configs[1]).  The flattened problem is resident in
 HBM before the timed region (ssfm_ba_create); each step restores the initial parameters on the device
 (ssfm_ba_reset) and runs ssfm_ba_run.  value = M * n_LM / t  with n_LM = linearisations over the K steps
-(SURVEY.md 8d), whole job, max time over ranks.
+(SURVEY.md 8d), whole job, max time over ranks; ms_per_step = the timed wall time / K.
+
+A plain run does only that: set up, warm up, time the K steps, print the record line (the headline keys and the configuration).  `--full` adds
+every side measurement described below (profiled step, rooflines, copy bandwidth, CPU baseline and parity, end-to-end calls, side paths, the
+configs[4]-size probe; for N > 1 the collective probe, configs4_sharded and pairwise_sharded) and writes the detail file.  `--dump-outputs DIR`
+writes what the last timed step computed (cameras, points, focal, summary) as DIR/<name>.npy; the inputs are seeded, identical from run to run.
 
 N > 1: points are sharded over ranks (cameras replicated), one RCCL all-reduce of the partial reduced system per
 LM iteration.  Default ("strong"): BASELINE.json's metric is THIS 300-camera problem at 1/2/4/8 GPUs, so the problem stays
@@ -94,6 +99,8 @@ def rocprof_avg_us():
 # 6 KB, strict JSON.  tests/test_bench_record_cpu.py builds it from a committed detail file and checks size and keys.
 RECORD_LIMIT = 6000
 REQUIRED_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline")
+# a plain run (no --full) measures the headline only: no profiled step, hence no roofline
+PLAIN_KEYS = tuple(k for k in REQUIRED_KEYS if k != "roofline")
 
 
 def _num(x, sig=6):
@@ -123,6 +130,8 @@ def compact_record(d):
     rec["config"] = {"workload": str(cfg.get("workload", ""))[:200], "camera_dof": cfg.get("camera_dof"), "lm_iterations_per_step": _num(cfg.get("lm_iterations_per_step")),
                      "sharding": cfg.get("sharding"), "comm": str(cfg.get("comm", ""))[:40], "reduced_solver": str(cfg.get("reduced_solver_short", "band-cholesky"))[:40],
                      "pcg_sweeps": cfg.get("pcg_sweeps")}
+    if "roofline" not in d:             # a plain run (no --full): the headline and its configuration only
+        return rec
     r = d.get("roofline") or {}
     rec["roofline"] = _pick(r, ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_us", "algorithmic_bytes_per_launch", "algorithmic_flop_per_launch", "executed_frac"))
     pm = d.get("pmc_profile") or {}
@@ -183,11 +192,12 @@ def compact_record(d):
     return rec
 
 
-def record_line(d):
-    """compact_record(d) as the single stdout line; raises if it is not a record the driver can keep (size, strict JSON, required keys)"""
+def record_line(d, full=True):
+    """compact_record(d) as the single stdout line; raises if it is not a record the driver can keep (size, strict JSON, required keys:
+    REQUIRED_KEYS for a --full run, PLAIN_KEYS for a plain one)"""
     rec = compact_record(d)
     line = json.dumps(rec, allow_nan=False, separators=(", ", ": "))
-    missing = [k for k in REQUIRED_KEYS if rec.get(k) is None and k != "vs_baseline"]
+    missing = [k for k in (REQUIRED_KEYS if full else PLAIN_KEYS) if rec.get(k) is None and k != "vs_baseline"]
     if missing or "\n" in line or len(line) >= RECORD_LIMIT:
         raise ValueError(f"bench record unusable: {len(line)} chars, missing {missing}")
     return line
@@ -207,6 +217,28 @@ def _jsonable(o):
         except Exception:
             return str(o)
     return o
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64.  Should they exceed DUMP_LIMIT_BYTES together (very large --points), the rows of the
+    largest ones are sampled: a fixed seeded choice of row indices, ascending, written beside them as DIR/<name>_rows.npy"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    for name in sorted(arrays, key=lambda k: -arrays[k].nbytes):
+        total = sum(a.nbytes for a in arrays.values())
+        a = arrays[name]
+        if total <= DUMP_LIMIT_BYTES or a.ndim == 0 or len(a) < 2:
+            break
+        row = a[0].nbytes + 8                                                       # a kept row + its index
+        keep = int(min(len(a), max(1, (DUMP_LIMIT_BYTES - (total - a.nbytes)) // row)))
+        rows = np.sort(np.random.default_rng(0).choice(len(a), size=keep, replace=False))
+        arrays[name] = a[rows]; arrays[name + "_rows"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def pair_kernel_flops(pairs):
@@ -571,8 +603,17 @@ def main():
     ap.add_argument("--no-collective-probe", action="store_true", help="N > 1: skip the timing probe that re-runs the sharded solve with its reductions switched off")
     ap.add_argument("--no-pairwise", action="store_true", help="N > 1: skip BASELINE configs[3] (exhaustive pairwise RANSAC) sharded over the N ranks")
     ap.add_argument("--pairwise-pairs", type=int, default=1999000, help="N > 1: image pairs of the pairwise_sharded leg (default: the 2000-frame exhaustive circle)")
-    ap.add_argument("--detail", default=None, help="where the full detail dictionary goes (default: bench_detail.json next to bench.py)")
+    ap.add_argument("--detail", default=None, help="--full: where the full detail dictionary goes (default: bench_detail.json next to bench.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the profiled step (per-kernel times, rooflines, PMC figures), the device copy bandwidth, "
+                         "the CPU baseline + parity + end-to-end calls, the side paths and the configs[4]-size probe (N = 1); the collective probe, configs[4] "
+                         "and configs[3] sharded (N > 1); writes the detail file.  The --no-* options above switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64): cameras (Nc, 6), points (Np, 3), "
+                         "focal (1,), summary (initial cost, final cost, iterations, successful steps, unsuccessful steps, termination)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import numpy as np
     import torch
@@ -645,6 +686,36 @@ def main():
     M = int(s["num_residual_blocks_global"])
     value = M * n_lm / elapsed
 
+    def headline():
+        """the keys of the result line that a plain run measures (a --full run adds its side measurements to them)"""
+        return {"metric": "BA obs/sec (Jac+Schur+PCG)", "value": value, "unit": "obs/s", "n_gpus": world, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": args.scaling,
+                "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+                "config": {"workload": f"{args.cameras} cams x {args.points} pts x {M} obs synthetic circle (BASELINE configs[1]" + (f" x {world}" if world > 1 and args.scaling == "weak" else "") + "), "
+                                       f"{args.mode} BA, focal {'free' if args.focal_free else 'fixed'}, CauchyLoss(1.0), Ceres-default LM",
+                           "reduced_solver": "exact block-banded Cholesky in Cuthill-McKee order (direct, like the reference's SPARSE_SCHUR); the PCG of the metric's name is a "
+                                             f"refinement that did not run: {s.get('pcg_iterations_total', 0)} sweeps in the last step",
+                           "reduced_solver_short": "band-cholesky (direct)", "pcg_sweeps": int(s.get("pcg_iterations_total", 0)),
+                           "camera_dof": s["camera_dof"], "lm_iterations_per_step": n_lm / args.steps, "sharding": f"points/{world}",
+                           "comm": ("none" if world == 1 else ("host-staged gloo (test configuration)" if host_comm else "rccl"))}}
+
+    if args.dump_outputs:
+        # what the last timed step computed, as a caller of ssfm_ba_run + ssfm_ba_download receives it (the download gathers every point on every rank)
+        cams_d, pts_d, f_d = [np.array(a, dtype=np.float64) for a in adj.download()]
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"cameras": cams_d, "points": pts_d, "focal": f_d.reshape(1),
+                                             "summary": np.array([s["initial_cost"], s["final_cost"], s["iterations"], s["num_successful_steps"],
+                                                                  s["num_unsuccessful_steps"], s["termination"]], dtype=np.float64)})
+
+    if not args.full:
+        if rank == 0:
+            sys.stdout.flush()
+            print(record_line(_jsonable(headline()), full=False), flush=True)
+        adj.close(); ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     # ---- per-kernel durations: one extra step with every launch bracketed by hipEvents on the solver's stream
     adj.set_profiling(True)
     sp = one_step()
@@ -714,15 +785,7 @@ def main():
             except Exception:
                 traffic = None
         out = {
-            "metric": "BA obs/sec (Jac+Schur+PCG)", "value": value, "unit": "obs/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"{args.cameras} cams x {args.points} pts x {M} obs synthetic circle (BASELINE configs[1]" + (f" x {world}" if world > 1 and args.scaling == "weak" else "") + "), "
-                                   f"{args.mode} BA, focal {'free' if args.focal_free else 'fixed'}, CauchyLoss(1.0), Ceres-default LM",
-                       "reduced_solver": "exact block-banded Cholesky in Cuthill-McKee order (direct, like the reference's SPARSE_SCHUR); the PCG of the metric's name is a "
-                                         f"refinement that did not run: {s.get('pcg_iterations_total', 0)} sweeps in the last step",
-                       "reduced_solver_short": "band-cholesky (direct)", "pcg_sweeps": int(s.get("pcg_iterations_total", 0)),
-                       "camera_dof": dc, "lm_iterations_per_step": n_lm / args.steps, "sharding": f"points/{world}", "comm": ("none" if world == 1 else ("host-staged gloo (test configuration)" if host_comm else "rccl"))},
+            **headline(),
             # The dominant kernel against the roof that bounds it.  k_schur_gram is a matrix-core kernel: ALGORITHMIC flop per launch (what the Schur assembly asks for
             # whatever the implementation: per observation one linearisation 150 + the half product 102 + the camera-side sums 132 + the upper triangle of its
             # diagonal Gram block 126; per observation pair the DC x DC x 3 multiply-adds of its off-diagonal block 216 -- DESIGN.md 4) / measured launch duration,

@@ -7,10 +7,11 @@
 TAG=${1:-r06f}; STAGE=${2:-bench}
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
 OUT=$GRAFT_REPO_ROOT/gpurun_out
+ROOT=$PWD
 first_csv() { find "$1" -name "$2" 2>/dev/null | head -1; }
 if [ "$STAGE" = "pmc" ]; then
   cd /tmp && export TMPDIR=/tmp
-  B="python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-scale-probe --no-side-paths"
+  B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-scale-probe --no-side-paths"
   timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG} -o ba -- $B --steps 5 --warmup 1 > $OUT/prof_${TAG}.log 2>&1
   F=$(first_csv $OUT/prof_${TAG} "*kernel_stats.csv"); [ -n "$F" ] && { cp "$F" $OUT/${TAG}_rocprofv3_kernel_stats.csv; head -12 "$F" | cut -c1-150; }
   timeout 400 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY SQ_WAIT_ANY --output-format csv -d $OUT/pmc1_${TAG} -o ba -- $B --steps 1 --warmup 0 > $OUT/pmc1_${TAG}.log 2>&1
@@ -32,11 +33,11 @@ if [ "$STAGE" = "pmc" ]; then
   F=$(first_csv $OUT/pmc_retri_${TAG} "*counter_collection.csv"); [ -n "$F" ] && cp "$F" $OUT/${TAG}_retri_counter_collection.csv
   tail -2 $OUT/pmc_retri_${TAG}.log
 else
-  timeout 900 python bench.py --steps 20 --warmup 5 --detail $OUT/bench_${TAG}_detail.json > $OUT/bench_${TAG}.json 2> $OUT/bench_${TAG}.err; tail -c 400 $OUT/bench_${TAG}.json; tail -2 $OUT/bench_${TAG}.err
-  timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 1 --comm host --pairwise-pairs 400000 --detail $OUT/bench_${TAG}_2ranks_host_detail.json > $OUT/bench_${TAG}_2ranks_host.json 2> $OUT/bench_${TAG}_2ranks_host.err
+  timeout 900 python bench.py --full --steps 20 --warmup 5 --detail $OUT/bench_${TAG}_detail.json > $OUT/bench_${TAG}.json 2> $OUT/bench_${TAG}.err; tail -c 400 $OUT/bench_${TAG}.json; tail -2 $OUT/bench_${TAG}.err
+  timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 5 --warmup 1 --comm host --pairwise-pairs 400000 --detail $OUT/bench_${TAG}_2ranks_host_detail.json > $OUT/bench_${TAG}_2ranks_host.json 2> $OUT/bench_${TAG}_2ranks_host.err
   tail -c 300 $OUT/bench_${TAG}_2ranks_host.json
-  timeout 300 python bench.py --steps 10 --warmup 2 --focal-free --no-side-paths --no-scale-probe --detail $OUT/bench_${TAG}_focalfree_detail.json > $OUT/bench_${TAG}_focalfree.json 2>> $OUT/bench_${TAG}.err
-  timeout 300 python bench.py --steps 10 --warmup 2 --mode spherical --no-side-paths --no-scale-probe --detail $OUT/bench_${TAG}_spherical_detail.json > $OUT/bench_${TAG}_spherical.json 2>> $OUT/bench_${TAG}.err
+  timeout 300 python bench.py --full --steps 10 --warmup 2 --focal-free --no-side-paths --no-scale-probe --detail $OUT/bench_${TAG}_focalfree_detail.json > $OUT/bench_${TAG}_focalfree.json 2>> $OUT/bench_${TAG}.err
+  timeout 300 python bench.py --full --steps 10 --warmup 2 --mode spherical --no-side-paths --no-scale-probe --detail $OUT/bench_${TAG}_spherical_detail.json > $OUT/bench_${TAG}_spherical.json 2>> $OUT/bench_${TAG}.err
   python3 -c "
 import json
 for v in ('focalfree','spherical'):

@@ -34,7 +34,7 @@ except Exception:
 sys.path.insert(0, ROOT)
 from bench import kernel_source_digest
 traffic["_meta"] = {"tag": tag, "kernel_source_sha16": kernel_source_digest(), "commit_at_collection": commit, "collected": datetime.date.today().isoformat(),
-                    "command": "bench.py --no-cpu-baseline --no-scale-probe --no-side-paths --steps 1 --warmup 0 under rocprofv3 --kernel-trace --pmc <one counter group per pass>"}
+                    "command": "bench.py --full --no-cpu-baseline --no-scale-probe --no-side-paths --steps 1 --warmup 0 under rocprofv3 --kernel-trace --pmc <one counter group per pass>"}
 traffic["_mfma_mops_f64"] = {re.sub(r"<.*>", "", k): d["SQ_INSTS_VALU_MFMA_MOPS_F64"] for k, d in out.items() if d.get("SQ_INSTS_VALU_MFMA_MOPS_F64", 0) > 0}   # per launch; one MOP = 512 flop
 traffic["_valu_wave_instructions"] = {re.sub(r"<.*>", "", k): d["SQ_INSTS_VALU"] for k, d in out.items() if "SQ_INSTS_VALU" in d}   # per launch, all waves
 json.dump(traffic, open(os.path.join(ROOT, "profiles", f"{tag}_pmc_traffic.json"), "w"), indent=1, sort_keys=True)

@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT
 FLAGS="$1"; shift
 for e in "$@"; do
   echo "== [$e]"
-  env $e python3 bench.py --steps 20 --warmup 3 --no-side-paths --no-scale-probe --no-cpu-baseline --detail /tmp/d.json $FLAGS 2>/tmp/err.txt | tail -1 | python3 -c "
+  env $e python3 bench.py --full --steps 20 --warmup 3 --no-side-paths --no-scale-probe --no-cpu-baseline --detail /tmp/d.json $FLAGS 2>/tmp/err.txt | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('  ms/step %.4f  value %.4e  us/iter(kernels) %s' % (d['ms_per_step'], d['value'], d.get('kernel_us_per_lm_iteration')))

@@ -12,6 +12,9 @@ ref_solver_C.npz    the generated coefficient arithmetic of both minimal solvers
                     `B(i,j)` -> array element, plain IEEE doubles in the written order -- no Eigen stand-in is compiled) for nullspace
                     bases B of random 3-ray samples; then the rest of each solver with numpy in place of Eigen's LU / EigenSolver
                     (:279-308, :623-654) and the compiled SolveQuartic: the candidate essential matrices.
+ref_ransaclib_line.txt, ref_sparse_trace.txt
+                    what tests/native/lomsac_driver_trace.cpp and tests/native/shim_maps_sanitize.cpp (-DSSFM_SPARSE_TRACE) print when compiled
+                    against the reference's include/RansacLib/ransac.h and include/sphericalsfm/sparse.hpp (native_traces()).
 ref_ransaclib.npz   traces of the reference's OWN include/RansacLib/{ransac,sampling,utils}.h (compiled as they stand, lomsac_reference.hpp)
                     driving the oracle's estimators: RansacStatistics, inlier sets and models for image pairs under many option sets
                     (row a13) and for the per-point runs of SfM::Retriangulate (row N1).
@@ -218,6 +221,21 @@ def retriangulate_trace():
     return dict(tri_points=pts, tri_num_inliers=nin, tri_iterations=it, tri_lo_runs=lo, tri_flags=fl)
 
 
+def native_traces():
+    """the two native harnesses built against the reference's own headers print the text fixtures their tests compare with:
+    tests/native/lomsac_driver_trace.cpp (include/RansacLib/ransac.h) -> ref_ransaclib_line.txt and
+    tests/native/shim_maps_sanitize.cpp -DSSFM_SPARSE_TRACE (include/sphericalsfm/sparse.hpp) -> ref_sparse_trace.txt"""
+    import tempfile
+    native = os.path.join(ROOT, "tests", "native")
+    for src, flags, out in (("lomsac_driver_trace.cpp", ["-O2", "-ffp-contract=off", "-DSSFM_TRACE_REFERENCE_HEADER"], "ref_ransaclib_line.txt"),
+                            ("shim_maps_sanitize.cpp", ["-O1", "-DSSFM_SPARSE_TRACE", "-DSSFM_REF_SPARSE"], "ref_sparse_trace.txt")):
+        with tempfile.TemporaryDirectory() as td:
+            exe = os.path.join(td, "trace")
+            subprocess.check_call(["g++", "-std=c++17", *flags, "-I" + os.path.join(REF, "include"), os.path.join(native, src), "-o", exe])
+            with open(os.path.join(HERE, out), "w") as f:
+                f.write(subprocess.run([exe], capture_output=True, text=True, check=True).stdout)
+
+
 def main():
     rng = np.random.default_rng(20261003)
     L = ref_lib()
@@ -249,6 +267,8 @@ def main():
     # 3. RansacLib
     d = pair_traces(); d.update(retriangulate_trace())
     np.savez_compressed(os.path.join(HERE, "ref_ransaclib.npz"), **d)
+    # 4. the text traces of the native harnesses
+    native_traces()
     print("quartic cases", len(coef), "| solver samples", S, "| pair traces", len(d["pair_seed"]), "| retriangulated points", len(d["tri_points"]))
 
 

@@ -2,6 +2,7 @@
 // std::map whose interface they implement: random operator[] / find / count / erase / iteration, in ascending and in random key order, under -fsanitize=address,undefined.
 // Built and run by tests/test_sanitizers_cpu.py.
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <random>
 #include "../../spherical_sfm_amd/csrc/shim/sfm.h"
@@ -72,8 +73,76 @@ static long run_reference(unsigned seed) {
     return sum;
 }
 #endif
+// -DSSFM_SPARSE_TRACE: the operation sequence of run_reference() applied to ONE side only -- the mirror's tables, or with -DSSFM_REF_SPARSE the
+// reference's SparseVector / SparseMatrix -- printing an FNV-1a digest of every lookup result and of the ordered contents (non-empty rows, entries, points)
+// at each checkpoint.  The reference side's output is the committed tests/golden/ref_sparse_trace.txt; the mirror's must print the same, line for line.
+struct MirrorSide {
+    IndexedMap<double> pts; std::map<int, FlatMap<double>> obs;
+    void set_obs(int r, int c, double v) { obs[r][c] = v; }
+    bool has_obs(int r, int c) { return obs.count(r) && obs[r].count(c); }
+    double get_obs(int r, int c) { return obs[r][c]; }
+    void erase_obs(int r, int c) { if (obs.count(r)) obs[r].erase(c); }
+    void erase_row(int r) { obs.erase(r); }
+    void set_pt(int c, double v) { pts[c] = v; }
+    bool has_pt(int c) { return pts.count(c) != 0; }
+    double get_pt(int c) { return pts[c]; }
+    void erase_pt(int c) { pts.erase(c); }
+    template <class F> void walk(F f) {
+        for (auto& row : obs) for (auto&& kv : row.second) f(row.first, kv.first, kv.second);
+        for (auto&& kv : pts) f(-1, kv.first, kv.second);
+    }
+};
+#ifdef SSFM_REF_SPARSE
+struct ReferenceSide {
+    SparseVector<double> pts; SparseMatrix<double> obs;
+    void set_obs(int r, int c, double v) { obs(r, c) = v; }
+    bool has_obs(int r, int c) { return obs.exists(r, c); }
+    double get_obs(int r, int c) { return obs(r, c); }
+    void erase_obs(int r, int c) { obs.erase(r, c); }
+    void erase_row(int r) { obs.erase(r); }
+    void set_pt(int c, double v) { pts(c) = v; }
+    bool has_pt(int c) { return pts.exists(c); }
+    double get_pt(int c) { return pts(c); }
+    void erase_pt(int c) { pts.erase(c); }
+    template <class F> void walk(F f) {
+        for (auto r = obs.begin(); r != obs.end(); ++r) for (auto e = r->second.begin(); e != r->second.end(); ++e) f(r->first, e->first, e->second);
+        for (auto q = pts.begin(); q != pts.end(); ++q) f(-1, q->first, q->second);
+    }
+};
+#endif
+template <class S> static void trace(unsigned seed) {
+    std::mt19937 rng(seed); S s; unsigned long long h = 1469598103934665603ull;
+    auto mix = [&](unsigned long long x) { h ^= x; h *= 1099511628211ull; };
+    auto bits = [](double v) { unsigned long long u; std::memcpy(&u, &v, sizeof u); return u; };
+    auto digest = [&](int step) {
+        long n = 0;
+        s.walk([&](int r, int c, double v) { mix((unsigned long long)(unsigned)r); mix((unsigned long long)(unsigned)c); mix(bits(v)); n++; });
+        std::printf("seed %u step %d entries %ld digest %016llx\n", seed, step, n, h);
+    };
+    for (int step = 0; step < 30000; step++) {
+        const int r = (int)(rng() % 40), c = (int)(rng() % 300), op = (int)(rng() % 8);
+        const double v = (double)(rng() % 1000);
+        if (op <= 1) s.set_obs(r, c, v);
+        else if (op == 2) { const bool a = s.has_obs(r, c); mix(a); if (a) mix(bits(s.get_obs(r, c))); }
+        else if (op == 3) s.erase_obs(r, c);
+        else if (op == 4) s.set_pt(c, v);
+        else if (op == 5) { const bool a = s.has_pt(c); mix(a); if (a) mix(bits(s.get_pt(c))); }
+        else if (op == 6) s.erase_pt(c);
+        else s.erase_row(r);
+        if (step % 1499 == 0) digest(step);
+    }
+    digest(30000);
+}
 int main() {
     std::setvbuf(stdout, nullptr, _IONBF, 0);
+#ifdef SSFM_SPARSE_TRACE
+#ifdef SSFM_REF_SPARSE
+    for (unsigned seed = 1; seed <= 4; seed++) trace<ReferenceSide>(seed);
+#else
+    for (unsigned seed = 1; seed <= 4; seed++) trace<MirrorSide>(seed);
+#endif
+    return 0;
+#endif
     long s = 0;
 #ifdef SSFM_REF_SPARSE
     for (unsigned seed = 1; seed <= 4; seed++) s += run_reference(seed);

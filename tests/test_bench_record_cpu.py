@@ -68,3 +68,34 @@ def test_record_refuses_a_line_without_the_contract_keys():
 
 def test_kernel_source_digest_is_stable():
     a = bench.kernel_source_digest(); assert len(a) == 16 and a == bench.kernel_source_digest()
+
+
+def test_plain_record_is_the_headline_alone():
+    """a plain run (no --full) prints the headline keys and the configuration, nothing that needs a run of its own"""
+    d = json.loads([l for l in open(os.path.join(ROOT, DETAILS[0])).read().splitlines() if l.startswith("{")][-1])
+    plain = {k: d[k] for k in bench.PLAIN_KEYS}
+    rec = json.loads(bench.record_line(plain, full=False))
+    assert set(rec) == set(bench.PLAIN_KEYS)
+    assert rec["value"] == pytest.approx(d["value"], rel=1e-5) and rec["ms_per_step"] == pytest.approx(d["ms_per_step"], rel=1e-5)
+    assert rec["unit"] == "obs/s" and rec["higher_is_better"] is True and rec["dtype"] == "f64" and rec["steps"] == d["steps"]
+    with pytest.raises(ValueError):
+        bench.record_line(plain)                                    # a --full record without its roofline is refused
+    with pytest.raises(ValueError):
+        bench.record_line({k: v for k, v in plain.items() if k != "ms_per_step"}, full=False)
+
+
+def test_dump_outputs_stays_within_its_limit(tmp_path, monkeypatch):
+    """--dump-outputs writes float64 .npy files; past the size limit the rows of the largest array are a fixed seeded sample, with their indices"""
+    import numpy as np
+    pts = np.arange(300000, dtype=np.float64).reshape(-1, 3); cams = np.ones((300, 6))
+    bench.dump_outputs(str(tmp_path / "a"), {"points": pts, "cameras": cams, "focal": np.array([1000.0])})
+    assert np.array_equal(np.load(tmp_path / "a" / "points.npy"), pts) and not (tmp_path / "a" / "points_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 20)
+    for run in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / run), {"points": pts, "cameras": cams, "focal": np.array([1000.0])})
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["cameras.npy", "focal.npy", "points.npy", "points_rows.npy"]
+    assert sum(np.load(tmp_path / "b" / f).nbytes for f in files) <= 1 << 20
+    p, r = np.load(tmp_path / "b" / "points.npy"), np.load(tmp_path / "b" / "points_rows.npy")
+    assert p.dtype == np.float64 and np.array_equal(p, pts[r.astype(np.int64)]) and np.array_equal(np.load(tmp_path / "b" / "cameras.npy"), cams)
+    assert np.array_equal(r, np.load(tmp_path / "c" / "points_rows.npy"))          # the same sample every run
