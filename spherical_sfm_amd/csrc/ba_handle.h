@@ -82,6 +82,9 @@ struct ssfm_ba_handle {
     DevBuf<double> zone; bool zone_views = false; size_t zone_len = 0, zone_nnz = 0, zone_n = 0;
     // SSFM_DETERMINISTIC=1 (det_acc.h): the assembly adds fixed-point limbs with integer atomics instead of doubles; k_det_decode turns them into the zone's doubles
     bool det = false; DevBuf<long long> det_limb, det_lacc; DevBuf<double> det_dfpart; size_t det_nacc = 0;
+    // det_lacc: the long accumulators of the scalar block, LA_STRIDE words for every entry of every replica
+    static constexpr size_t det_lacc_words = (size_t)SC_NSLOT * SC_TOTAL * LA_STRIDE;
+    hipError_t clear_det_lacc() { return hipMemsetAsync(det_lacc.p, 0, det_lacc_words * sizeof(long long), ctx->stream); }
     void set_zone(int which) {
         scal.p = zone.p + (size_t)which * zone_len; pcg.p = scal.p + scal.n; redbuf.p = pcg.p + pcg.n;
         S_val = redbuf.p; rhs = S_val + zone_nnz; Udiag = rhs + (zone_n + 1); Sfc = Udiag + zone_n; gcraw = Sfc + zone_n; red_scal = gcraw + zone_n;

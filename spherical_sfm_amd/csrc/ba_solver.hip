@@ -28,251 +28,324 @@
 
 namespace ssfm {
 
+// SSFM_DETERMINISTIC=1 (det_acc.h): the scalars a decode launch / k_publish folds from the long accumulators, as a mask over the scalar block
+constexpr unsigned DET_K_ASSEMBLY = (1u << SC_COST) | (1u << SC_FJJ) | (1u << SC_FJR) | (1u << SC_FWW) | (1u << SC_FWG);
+constexpr unsigned DET_K_TAIL = (1u << SC_MODEL) | (1u << SC_STEP2_PT) | (1u << SC_XN2_PT) | (1u << SC_CAND_COST) | (1u << SC_STEP2_CAM) | (1u << SC_XN2_CAM);
+// deterministic mode: the tail's sums (model change, step and candidate norms, candidate cost) sit in the long accumulators; k_publish folds them itself,
+// the copying hand-over needs them as doubles in replica 0 first
+static unsigned det_tail_mask(bool with_cams, bool gram_fold) {
+    // (with_cams: k_cam_update, one workgroup, has STORED the two camera norms in replica 0 -- they are not in the long accumulators)
+    const unsigned tail = with_cams ? (DET_K_TAIL & ~((1u << SC_STEP2_CAM) | (1u << SC_XN2_CAM))) : DET_K_TAIL;
+    return tail | (gram_fold ? (1u << SC_COST) : 0u);   // (gram_fold: the cost was not decoded behind the assembly)
+}
+
+enum LmStep { LM_ACCEPTED, LM_REJECTED, LM_INVALID, LM_TERMINATED };      // what LmRun::decide made of an iteration (LM_TERMINATED: the reason is in the summary)
+
+// One solve: the state of the trust-region loop and its phases, in the order run() calls them.
 template <int DC>
-static int lm_loop(ssfm_ba_handle* h, ssfm_ba_summary* S) {
-    ssfm_ctx* ctx = h->ctx; hipStream_t st = ctx->stream;
-    const BAFlat& F = h->F; const ssfm_ba_options& O = h->opt;
-    const int Nc = F.Nc, nP = F.nP;
-    const int loss = O.loss_type; const double la = O.loss_scale;
-    const int gp_pts = (nP + 255) / 256, gp_cam = (Nc + 63) / 64;
+struct LmRun {
+    ssfm_ba_handle* const h; ssfm_ba_summary* const S;
+    ssfm_ctx* const ctx; const hipStream_t st; const BAFlat& F; const ssfm_ba_options& O;
+    const int Nc, nP, loss; const double la; const int gp_cam;
+    const double2* const oxy;
+    long long* const lacc;                                           // SSFM_DETERMINISTIC=1: the scalar block's long accumulators
+    struct State { double *cam, *rot, *pts, *focal; } x, c;           // x and the candidate: swapped when a step is accepted
+    // with the banded factor and the lower-triangle storage the arrow kernel of the solve also writes the candidate cameras
+    const bool fused_cams, residual_later;
+    // per-phase device times (summary.t_kernel_*_ms) cost five event records and four queries per iteration, the queries on the
+    // host's critical path between two iterations: only with profiling on (ssfm_ba_set_profiling) or options.verbose
+    const bool phases;
+    // the knobs of a solve (read_knobs)
+    bool poll = false, spec_on = false, fuse_lin = false; int gram_bs = -1, gbs_split_env = 0;
+    double *host_scal = nullptr, *host_pcg1 = nullptr;               // the iteration's scalars and solver flags as the host reads them
+    // trust region
+    double radius, decrease_factor = 2.0, x_norm = 0.0, x_cost = 0.0, minimum_cost = std::numeric_limits<double>::max();
+    int iteration = 0, num_invalid = 0;
+    bool last_successful = true, x0_pending = true;
+    // speculation: lin_done = this iteration's k_point_lin ran behind the previous one; what the device decided for the launch behind this one (it ran iff dev_go)
+    bool lin_done = false, spec_launched = false, dev_go = false; double dev_radius = 0.0;
+    int pcg_iters = 0; bool pcg_ok = false;
+    float ms_lin = 0, ms_schur = 0, ms_pcg = 0, ms_upd = 0;
+#ifdef SSFM_LAB
+    DevBuf<double> probe_Y, probe_S;                                 // SSFM_PAIRS_Y_PROBE
+#endif
+
+    LmRun(ssfm_ba_handle* h_, ssfm_ba_summary* S_)
+        : h(h_), S(S_), ctx(h_->ctx), st(h_->ctx->stream), F(h_->F), O(h_->opt), Nc(F.Nc), nP(F.nP), loss(O.loss_type), la(O.loss_scale), gp_cam((Nc + 63) / 64),
+          oxy(reinterpret_cast<const double2*>(h_->obs_xy.p)), lacc(h_->det ? h_->det_lacc.p : (long long*)nullptr),
+          x{h_->cam_x.p, h_->rot_x.p, h_->pts_x.p, h_->focal3.p}, c{h_->cam_c.p, h_->rot_c.p, h_->pts_c.p, h_->focal3.p + 1},
+          fused_cams(O.preconditioner == 0 && F.sym_lower), residual_later(fused_cams && nP > 0), phases(h_->profile || O.verbose), radius(O.initial_trust_region_radius) {}
+
+    // ---- lab knobs (knobs.h: the shipped library compiles the defaults in) ----
     // lane-per-point kernels of the LM loop run as single-wave workgroups: 4x more workgroups spread evenly over the CUs
-    static const int PTB = SSFM_LAB_KNOB("SSFM_PT_BLOCK", 256);
-    const int gp_pts_lm = (nP + PTB - 1) / PTB;
-    static const int PLB = SSFM_LAB_KNOB("SSFM_PL_BLOCK", 64);      // k_point_lin has no workgroup-level step: one wave per workgroup spreads best
-    const double2* oxy = reinterpret_cast<const double2*>(h->obs_xy.p);
-    double* fx = h->focal3.p; double* fc = h->focal3.p + 1;
-    double* cam_x = h->cam_x.p; double* cam_c = h->cam_c.p; double* pts_x = h->pts_x.p; double* pts_c = h->pts_c.p;
-    double* rot_x = h->rot_x.p; double* rot_c = h->rot_c.p;
-    // the only host round trip of an iteration = its scalars [sums | gradient max | solver flags].
-    // default: the last kernel of an iteration (k_publish) writes the folded scalars + flags into coherent pinned memory and the host
-    // spins on its sequence number (ba_handle.h lm_poll / publish_alloc / wait_published); SSFM_LM_POLL=0: copy of all replicas +
-    // stream synchronisation + host fold
-    const bool poll = lm_poll() && publish_alloc(h);
-    if (!poll && !h->host_sp) SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&h->host_sp, (SC_NSLOT * SC_TOTAL + PCG_TOTAL + 1) * sizeof(double), hipHostMallocDefault));
-    double* host_sp = h->host_sp;
-    double* host_scal = poll ? h->host_pub : host_sp; double* host_pcg1 = poll ? h->host_pub + SC_TOTAL : host_sp + SC_NSLOT * SC_TOTAL;
-    auto wait_iteration = [&]() -> int {
+    static int pt_block() { return SSFM_LAB_KNOB("SSFM_PT_BLOCK", 256); }
+    static int pl_block() { return SSFM_LAB_KNOB("SSFM_PL_BLOCK", 64); }      // k_point_lin has no workgroup-level step: one wave per workgroup spreads best
+    // EXPERIMENT, off (SSFM_PUBLISH_FUSED=1): the end-of-iteration hand-over in the last workgroup of k_point_backsub (arrival ticket) instead of a k_publish
+    // launch.  Measured: k_point_backsub 22.8 -> 55.9 us at config 2 and 380 -> 1290 us at the configs[4] size -- every workgroup needs an agent-scope release
+    // fence (an L2 write-back on this multi-XCD part) + a same-address atomic before it may leave, which costs far more than the 4.7 us launch it saves.
+    static bool fused_publish() { return SSFM_LAB_KNOB("SSFM_PUBLISH_FUSED", 0) != 0; }
+    static bool zone_clear_fused() { return SSFM_LAB_KNOB("SSFM_ZONE_CLEAR_FUSED", 1) != 0; }
+
+    // ---- the zones: an iteration works in zone (iteration & 1) while the other one is cleared for the next ----
+    // [scalars | solver flags | S | rhs | diag U | S_fc | Jc^T r | sums]; det: where the limbs of the zone's accumulators / the partial blocks of the atomics-free
+    // Gram emission live; fold_*: what k_finalize_gather folds first when that emission is in use (gram_fold), null otherwise
+    struct ZoneView { double *scal, *S_val, *rhs, *Udiag, *Sfc, *gcraw; DetZone det; const double* fold_part; long long* fold_lacc; };
+    ZoneView zone(int iter) const {
+        ZoneView z; z.scal = h->zone.p + (size_t)(iter & 1) * h->zone_len;
+        z.S_val = z.scal + h->scal.n + h->pcg.n; z.rhs = z.S_val + h->zone_nnz; z.Udiag = z.rhs + (h->zone_n + 1); z.Sfc = z.Udiag + h->zone_n; z.gcraw = z.Sfc + h->zone_n;
+        if (h->det) { z.det.base = z.S_val; z.det.limb = h->det_limb.p + 1; }
+        if (h->gram_fold) { z.det.part = h->gram_part.p; z.det.part_off = h->gpart_off.p; }
+        z.fold_part = h->gram_fold ? h->gram_part.p : (const double*)nullptr; z.fold_lacc = h->gram_fold ? lacc : (long long*)nullptr;
+        return z;
+    }
+    // the next iteration's zone is cleared by the finalize kernel (a slice per workgroup) when its length allows 16-byte stores, by a memset behind the tail otherwise
+    struct NextClear { double* zone; double2* in_finalize; size_t len2; };
+    NextClear next_clear() const {
+        NextClear n; n.zone = zone(iteration + 1).scal;
+        const bool fused = O.preconditioner == 0 && zone_clear_fused() && (h->zone_len % 2 == 0) && ((reinterpret_cast<uintptr_t>(n.zone) & 15) == 0);
+        n.in_finalize = fused ? reinterpret_cast<double2*>(n.zone) : (double2*)nullptr; n.len2 = fused ? h->zone_len / 2 : 0;
+        return n;
+    }
+    // limbs -> the zone's doubles (matrices; cleared as they are read), long accumulators of kmask -> replica 0 of the scalar block
+    void det_decode(const ZoneView& z, bool matrices, unsigned kmask) {
+        const int gz = matrices ? (int)std::min<size_t>(512, (h->det_nacc + 255) / 256) : 0;
+        LAUNCH(h, KID_DET_DECODE, k_det_decode, gz + 1, 256, 0, z.S_val, h->det_limb.p + 1, h->det_nacc, gz, z.scal, h->det_lacc.p, kmask);
+    }
+    int record_phase(int i) { if (phases) SSFM_HIP_CHECK(ctx, hipEventRecord(h->phase_ev[i], st)); return SSFM_OK; }
+
+    // ---- the hand-over to the host ----
+    int wait_iteration() {
         if (!poll || h->profile || (h->opt.verbose != 0)) SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        return poll ? wait_published(h) : SSFM_OK;
-    };
-    auto fold_host_scal = [&]() {                                    // replicas -> replica 0 (sums; the gradient max by max)
-        for (int k = 0; k < SC_TOTAL; k++) {
-            double a = host_sp[k];
-            for (int s2 = 1; s2 < SC_NSLOT; s2++) { const double v = host_sp[(size_t)s2 * SC_TOTAL + k]; a = (k == SC_GMAX) ? std::max(a, v) : a + v; }
-            host_sp[k] = a;
+        const int rc = poll ? wait_published(h) : SSFM_OK; if (rc) return rc;
+        if (!poll) {                                                 // replicas -> replica 0 (sums; the gradient max by max)
+            double* host_sp = h->host_sp;
+            for (int k = 0; k < SC_TOTAL; k++) {
+                double a = host_sp[k];
+                for (int s2 = 1; s2 < SC_NSLOT; s2++) { const double v = host_sp[(size_t)s2 * SC_TOTAL + k]; a = (k == SC_GMAX) ? std::max(a, v) : a + v; }
+                host_sp[k] = a;
+            }
         }
-    };
-    // ---- iteration 0: rotation tables, Jacobi scaling from the initial Jacobian, |x|
-    h->set_zone(0);
-    if (h->det) {   // a solve starts on clean limbs whatever the previous one on this handle left (normally nothing: every decode clears what it read)
-        if (!h->gram_fold) SSFM_HIP_CHECK(ctx, hipMemsetAsync(h->det_limb.p, 0, (2 * h->det_nacc + 2) * sizeof(long long), st));      // (atomics-free emission: no limbs in use)
-        SSFM_HIP_CHECK(ctx, hipMemsetAsync(h->det_lacc.p, 0, (size_t)SC_NSLOT * SC_TOTAL * LA_STRIDE * sizeof(long long), st));
+        return SSFM_OK;
     }
-    // four launches: [rotation tables + clears] [point column norms + scales] [camera column norms + scales] [|x|^2 + focal scale]
-    const bool make_scale = !h->scale_ready;
-    LAUNCH(h, KID_CAM_ROT, k_cam_rot0, gp_cam, 64, 0, cam_x, rot_x, Nc, h->scal.p, (int)SC_TOTAL, h->diag_f.p, make_scale ? 1 : 0);
-    if (make_scale) {
-        if (nP > 0) hipLaunchKernelGGL(k_colnorm_both, dim3(gp_pts + Nc), dim3(256), 0, st, gp_pts, cam_x, rot_x, pts_x, fx, oxy, h->obs_cam.p, h->pt_start.p, nP,
-                                       loss, la, h->diag_pt.p, h->diag_f.p, h->mask_pt.p, h->scale_pt.p, O.jacobi_scaling, h->det ? h->det_dfpart.p : (double*)nullptr,
-                                       h->obs_pt.p, h->cam_start.p, h->cam_obs.p, h->diag_cam.p, h->mask_cam.p, ctx->collective ? (double*)nullptr : h->scale_cam.p);
-        else hipLaunchKernelGGL(k_colnorm_cam, dim3(Nc), dim3(256), 0, st, cam_x, rot_x, pts_x, fx, oxy, h->obs_pt.p, h->cam_start.p, h->cam_obs.p,
-                           loss, la, h->diag_cam.p, h->mask_cam.p, ctx->collective ? (double*)nullptr : h->scale_cam.p, O.jacobi_scaling);
-        if (ctx->collective) {   // camera / focal column norms are sums over every rank's observations
-            int rc = allreduce(h, h->diag_cam.p, (size_t)Nc * 6, ncclSum); if (rc) return rc;
-            rc = allreduce(h, h->diag_f.p, 1, ncclSum); if (rc) return rc;
-        }
-        h->scale_ready = true;
-    }
-    {
-        // (at most 256 + 16 workgroups: each ends in one atomic on the same two scalars, ~12 ns apiece -- 17.6k of them at 1.5 M points took 217 us, 1032 at config 2 15 us)
-        const int gpt = nP > 0 ? std::min(256, (nP * 3 + 255) / 256) : 0, gcm = std::min(16, (Nc * 6 + 255) / 256);
-        hipLaunchKernelGGL(k_startup_tail, dim3(gpt + gcm), dim3(256), 0, st, pts_x, h->mask_pt.p, nP * 3, gpt, cam_x, h->mask_cam.p, Nc * 6, fx, h->mask_f.p,
-                           h->diag_cam.p, (make_scale && ctx->collective) ? h->scale_cam.p : (double*)nullptr, h->diag_f.p, make_scale ? h->scale_f.p : (double*)nullptr,
-                           O.jacobi_scaling, h->scal.p + SC_X0N2_PT, h->scal.p + SC_X0N2_CAM, (make_scale && h->det && nP > 0) ? h->det_dfpart.p : (const double*)nullptr, gp_pts,
-                           (const double*)h->scal.p, h->det ? h->det_lacc.p : (long long*)nullptr);
-        if (h->det) LAUNCH(h, KID_DET_DECODE, k_det_decode, 1, 256, 0, h->S_val, h->det_limb.p + 1, h->det_nacc, 0, h->scal.p, h->det_lacc.p, (1u << SC_X0N2_PT) | (1u << SC_X0N2_CAM));
-    }
-    { int rc = allreduce(h, h->scal.p + SC_X0N2_PT, 1, ncclSum); if (rc) return rc; }
-    SSFM_HIP_CHECK(ctx, hipMemcpyAsync(host_scal, h->scal.p, SC_TOTAL * sizeof(double), hipMemcpyDeviceToHost, st));
     // |x_0| is first needed when iteration 0's tail is enqueued (the device-side gate takes it as an argument): the host waits for the copy THERE, behind the kernels of
-    // iteration 0's assembly and solve -- a stream synchronisation here left the GPU idle for the host's wake-up and first launches (~20 us per solve)
-    if (!h->x0_ev) SSFM_HIP_CHECK(ctx, hipEventCreateWithFlags(&h->x0_ev, hipEventDisableTiming));
-    SSFM_HIP_CHECK(ctx, hipEventRecord(h->x0_ev, st));
-    double x_norm = 0.0; bool x0_pending = true;
-    auto need_x0 = [&]() -> int {
+    // iteration 0's assembly and solve -- a stream synchronisation at the start left the GPU idle for the host's wake-up and first launches (~20 us per solve)
+    int need_x0() {
         if (!x0_pending) return SSFM_OK;
         SSFM_HIP_CHECK(ctx, hipEventSynchronize(h->x0_ev));
         x_norm = std::sqrt(host_scal[SC_X0N2_PT] + host_scal[SC_X0N2_CAM]); x0_pending = false;
         return SSFM_OK;
-    };
-
-    SSFM_HIP_CHECK(ctx, hipMemsetAsync(h->zone.p + h->zone_len, 0, h->zone_len * sizeof(double), st));   // zone of iteration 1
-    double radius = O.initial_trust_region_radius, decrease_factor = 2.0;
-    double x_cost = 0.0, minimum_cost = std::numeric_limits<double>::max();
-    int iteration = 0, num_invalid = 0;
-    bool last_successful = true;
-    S->num_successful_steps = 1; S->num_unsuccessful_steps = 0; S->num_linearizations = 0; S->pcg_iterations_total = 0;
-    S->termination = SSFM_NO_CONVERGENCE;
-    float ms_lin = 0, ms_schur = 0, ms_pcg = 0, ms_upd = 0;
-    // Speculation: k_publish also decides "accepted, go on" + the next radius on the device (LmGate), and the next iteration's
-    // k_point_lin is queued right behind it, reading both from device memory -- it runs while the host wakes up, decides and
-    // launches the rest.  The host's own decision stays authoritative: a speculative launch that should not have run only touched
-    // scratch arrays and the next zone, which is then cleared again.  SSFM_LM_SPECULATE=0 turns it off.
-    const char* e_spec = std::getenv("SSFM_LM_SPECULATE");
-    const bool spec_on = poll && nP > 0 && !(e_spec && std::atoi(e_spec) == 0);
-    bool lin_done = false, spec_launched = false;
-    const int gram_bs_env = std::getenv("SSFM_GRAM_BACKSUB") ? std::atoi(std::getenv("SSFM_GRAM_BACKSUB")) : -1;      // read once per solve (tests switch it between solves)
-    // Round 5 EXPERIMENT, off (SSFM_GRAM_FUSE=1): when every point sits in a signature group, k_schur_gram does the point pass itself (ba_kernels.h: FUSE) and k_point_lin
-    // does not run; the speculative launch behind k_publish is then the Gram kernel of the NEXT iteration, accumulating into the next zone.  Correct (parity 3e-11, same
-    // iterations) and SLOWER: 97.6 us against 43.7 + 18.3 at config 2, 1357 against 409 + 179 at the configs[4] size -- the Gram kernel sits at its register limit
-    // (256 at two waves per SIMD: 39 camera sums, the tile accumulators, one observation's linearisation) and the point pass's fold spills 43-80 of them to scratch
-    // (profiles/r05_notes.md).  One launch less is not worth a kernel that leaves its registers.
-    static const bool gram_fuse_env = SSFM_LAB_KNOB("SSFM_GRAM_FUSE", 0) != 0;
-    const bool fuse_lin = gram_fuse_env && nP > 0 && !F.gr_rec.empty() && F.gram_points == (int64_t)nP && F.chunk_cam.empty() && F.cs_task_cam.empty();
-    struct ZonePtrs { double *scal, *S_val, *rhs, *Udiag, *Sfc, *gcraw; };
-    auto zone_ptrs = [&](int which) { ZonePtrs z; z.scal = h->zone.p + (size_t)which * h->zone_len; double* red = z.scal + h->scal.n + h->pcg.n;
-                                      z.S_val = red; z.rhs = z.S_val + h->zone_nnz; z.Udiag = z.rhs + (h->zone_n + 1); z.Sfc = z.Udiag + h->zone_n; z.gcraw = z.Sfc + h->zone_n; return z; };
-    // SSFM_DETERMINISTIC=1 (det_acc.h): where the limbs of a zone's accumulators live; the scalar block's long accumulators; the decode launches
-    long long* const lacc = h->det ? h->det_lacc.p : (long long*)nullptr;
-    auto det_zone = [&](const ZonePtrs& z) { DetZone dz; if (h->det) { dz.base = z.S_val; dz.limb = h->det_limb.p + 1; } if (h->gram_fold) { dz.part = h->gram_part.p; dz.part_off = h->gpart_off.p; } return dz; };
-    constexpr unsigned DET_K_ASSEMBLY = (1u << SC_COST) | (1u << SC_FJJ) | (1u << SC_FJR) | (1u << SC_FWW) | (1u << SC_FWG);
-    constexpr unsigned DET_K_TAIL = (1u << SC_MODEL) | (1u << SC_STEP2_PT) | (1u << SC_XN2_PT) | (1u << SC_CAND_COST) | (1u << SC_STEP2_CAM) | (1u << SC_XN2_CAM);
-    auto det_decode = [&](const ZonePtrs& z, bool matrices, unsigned kmask) {
-        const int gz = matrices ? (int)std::min<size_t>(512, (h->det_nacc + 255) / 256) : 0;
-        LAUNCH(h, KID_DET_DECODE, k_det_decode, gz + 1, 256, 0, z.S_val, h->det_limb.p + 1, h->det_nacc, gz, z.scal, h->det_lacc.p, kmask);
-    };
-    // EXPERIMENT, off (SSFM_PUBLISH_FUSED=1): the end-of-iteration hand-over in the last workgroup of k_point_backsub (arrival ticket) instead of a k_publish
-    // launch.  Measured: k_point_backsub 22.8 -> 55.9 us at config 2 and 380 -> 1290 us at the configs[4] size -- every workgroup needs an agent-scope release
-    // fence (an L2 write-back on this multi-XCD part) + a same-address atomic before it may leave, which costs far more than the 4.7 us launch it saves.
-    static const bool fused_publish = SSFM_LAB_KNOB("SSFM_PUBLISH_FUSED", 0) != 0;
-    if (fused_publish && poll && !h->pub_ticket.p) {
-        SSFM_HIP_CHECK(ctx, h->pub_ticket.alloc(1)); SSFM_HIP_CHECK(ctx, hipMemsetAsync(h->pub_ticket.p, 0, sizeof(int), st));
     }
-    static const bool zone_clear_fused = SSFM_LAB_KNOB("SSFM_ZONE_CLEAR_FUSED", 1) != 0;
-    // per-phase device times (summary.t_kernel_*_ms) cost five event records and four queries per iteration, the queries on the
-    // host's critical path between two iterations: only with profiling on (ssfm_ba_set_profiling) or options.verbose
-    const bool phases = h->profile || O.verbose;
-    if (phases) for (auto& e : h->phase_ev) if (!e) SSFM_HIP_CHECK(ctx, hipEventCreate(&e));
 
-    // SSFM_PAIRS_Y_PROBE=1: the half-product variant of the pair pass runs next to the real kernel, on scratch data, for rocprofv3
-    const bool y_probe = SSFM_LAB_KNOB("SSFM_PAIRS_Y_PROBE", 0) != 0;
-    DevBuf<double> probe_Y, probe_S;
-    if (y_probe) {
-        SSFM_HIP_CHECK(ctx, probe_Y.alloc((size_t)F.M * DC * 3)); SSFM_HIP_CHECK(ctx, probe_S.alloc(h->zone_nnz));
-        SSFM_HIP_CHECK(ctx, hipMemsetAsync(probe_Y.p, 0x3c, (size_t)F.M * DC * 3 * sizeof(double), st)); SSFM_HIP_CHECK(ctx, hipMemsetAsync(probe_S.p, 0, h->zone_nnz * sizeof(double), st));
+    // The knobs of a solve, read once at its start (tests switch them between solves; the plan cache reuses handles, so not per handle).
+    int read_knobs() {
+        // the only host round trip of an iteration = its scalars [sums | gradient max | solver flags].
+        // default: the last kernel of an iteration (k_publish) writes the folded scalars + flags into coherent pinned memory and the host
+        // spins on its sequence number (ba_handle.h lm_poll / publish_alloc / wait_published); SSFM_LM_POLL=0: copy of all replicas +
+        // stream synchronisation + host fold
+        poll = lm_poll() && publish_alloc(h);
+        if (!poll && !h->host_sp) SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&h->host_sp, (SC_NSLOT * SC_TOTAL + PCG_TOTAL + 1) * sizeof(double), hipHostMallocDefault));
+        host_scal = poll ? h->host_pub : h->host_sp; host_pcg1 = poll ? h->host_pub + SC_TOTAL : h->host_sp + SC_NSLOT * SC_TOTAL;
+        // Speculation: k_publish also decides "accepted, go on" + the next radius on the device (LmGate), and the next iteration's
+        // k_point_lin is queued right behind it, reading both from device memory -- it runs while the host wakes up, decides and
+        // launches the rest.  The host's own decision stays authoritative: a speculative launch that should not have run only touched
+        // scratch arrays and the next zone, which is then cleared again.  SSFM_LM_SPECULATE=0 turns it off.
+        spec_on = poll && nP > 0 && knob_env_int("SSFM_LM_SPECULATE", 1) != 0;
+        gram_bs = knob_env_int("SSFM_GRAM_BACKSUB", -1);             // 0 / 1 forces k_gram_backsub2 off / on (back_substitute)
+        gbs_split_env = knob_env_int("SSFM_GBS_SPLIT", 0);           // > 0: waves per task of k_gram_backsub2
+        // Round 5 EXPERIMENT, off (SSFM_GRAM_FUSE=1): when every point sits in a signature group, k_schur_gram does the point pass itself (ba_kernels.h: FUSE) and k_point_lin
+        // does not run; the speculative launch behind k_publish is then the Gram kernel of the NEXT iteration, accumulating into the next zone.  Correct (parity 3e-11, same
+        // iterations) and SLOWER: 97.6 us against 43.7 + 18.3 at config 2, 1357 against 409 + 179 at the configs[4] size -- the Gram kernel sits at its register limit
+        // (256 at two waves per SIMD: 39 camera sums, the tile accumulators, one observation's linearisation) and the point pass's fold spills 43-80 of them to scratch
+        // (profiles/r05_notes.md).  One launch less is not worth a kernel that leaves its registers.
+        fuse_lin = SSFM_LAB_KNOB("SSFM_GRAM_FUSE", 0) != 0 && nP > 0 && !F.gr_rec.empty() && F.gram_points == (int64_t)nP && F.chunk_cam.empty() && F.cs_task_cam.empty();
+        return SSFM_OK;
     }
-    while (true) {
-        if (iteration >= O.max_num_iterations) { S->termination = SSFM_NO_CONVERGENCE; break; }
-        if (radius <= O.min_trust_region_radius) { S->termination = SSFM_CONVERGENCE; break; }
-        iteration++;
-        // ================= assemble at x with the current radius =================
+
+    // ---- iteration 0: rotation tables, Jacobi scaling from the initial Jacobian, |x|
+    int startup() {
+        { const int rc = read_knobs(); if (rc) return rc; }
+        const int gp_pts = (nP + 255) / 256;
+        h->set_zone(0);
+        if (h->det) {   // a solve starts on clean limbs whatever the previous one on this handle left (normally nothing: every decode clears what it read)
+            if (!h->gram_fold) SSFM_HIP_CHECK(ctx, hipMemsetAsync(h->det_limb.p, 0, (2 * h->det_nacc + 2) * sizeof(long long), st));      // (atomics-free emission: no limbs in use)
+            SSFM_HIP_CHECK(ctx, h->clear_det_lacc());
+        }
+        // four launches: [rotation tables + clears] [point column norms + scales] [camera column norms + scales] [|x|^2 + focal scale]
+        const bool make_scale = !h->scale_ready;
+        LAUNCH(h, KID_CAM_ROT, k_cam_rot0, gp_cam, 64, 0, x.cam, x.rot, Nc, h->scal.p, (int)SC_TOTAL, h->diag_f.p, make_scale ? 1 : 0);
+        if (make_scale) {
+            if (nP > 0) hipLaunchKernelGGL(k_colnorm_both, dim3(gp_pts + Nc), dim3(256), 0, st, gp_pts, x.cam, x.rot, x.pts, x.focal, oxy, h->obs_cam.p, h->pt_start.p, nP,
+                                           loss, la, h->diag_pt.p, h->diag_f.p, h->mask_pt.p, h->scale_pt.p, O.jacobi_scaling, h->det ? h->det_dfpart.p : (double*)nullptr,
+                                           h->obs_pt.p, h->cam_start.p, h->cam_obs.p, h->diag_cam.p, h->mask_cam.p, ctx->collective ? (double*)nullptr : h->scale_cam.p);
+            else hipLaunchKernelGGL(k_colnorm_cam, dim3(Nc), dim3(256), 0, st, x.cam, x.rot, x.pts, x.focal, oxy, h->obs_pt.p, h->cam_start.p, h->cam_obs.p,
+                               loss, la, h->diag_cam.p, h->mask_cam.p, ctx->collective ? (double*)nullptr : h->scale_cam.p, O.jacobi_scaling);
+            if (ctx->collective) {   // camera / focal column norms are sums over every rank's observations
+                int rc = allreduce(h, h->diag_cam.p, (size_t)Nc * 6, ncclSum); if (rc) return rc;
+                rc = allreduce(h, h->diag_f.p, 1, ncclSum); if (rc) return rc;
+            }
+            h->scale_ready = true;
+        }
+        {
+            // (at most 256 + 16 workgroups: each ends in one atomic on the same two scalars, ~12 ns apiece -- 17.6k of them at 1.5 M points took 217 us, 1032 at config 2 15 us)
+            const int gpt = nP > 0 ? std::min(256, (nP * 3 + 255) / 256) : 0, gcm = std::min(16, (Nc * 6 + 255) / 256);
+            hipLaunchKernelGGL(k_startup_tail, dim3(gpt + gcm), dim3(256), 0, st, x.pts, h->mask_pt.p, nP * 3, gpt, x.cam, h->mask_cam.p, Nc * 6, x.focal, h->mask_f.p,
+                               h->diag_cam.p, (make_scale && ctx->collective) ? h->scale_cam.p : (double*)nullptr, h->diag_f.p, make_scale ? h->scale_f.p : (double*)nullptr,
+                               O.jacobi_scaling, h->scal.p + SC_X0N2_PT, h->scal.p + SC_X0N2_CAM, (make_scale && h->det && nP > 0) ? h->det_dfpart.p : (const double*)nullptr, gp_pts,
+                               (const double*)h->scal.p, lacc);
+            if (h->det) LAUNCH(h, KID_DET_DECODE, k_det_decode, 1, 256, 0, h->S_val, h->det_limb.p + 1, h->det_nacc, 0, h->scal.p, h->det_lacc.p, (1u << SC_X0N2_PT) | (1u << SC_X0N2_CAM));
+        }
+        { int rc = allreduce(h, h->scal.p + SC_X0N2_PT, 1, ncclSum); if (rc) return rc; }
+        SSFM_HIP_CHECK(ctx, hipMemcpyAsync(host_scal, h->scal.p, SC_TOTAL * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (!h->x0_ev) SSFM_HIP_CHECK(ctx, hipEventCreateWithFlags(&h->x0_ev, hipEventDisableTiming));      // need_x0 waits for it
+        SSFM_HIP_CHECK(ctx, hipEventRecord(h->x0_ev, st));
+        SSFM_HIP_CHECK(ctx, hipMemsetAsync(zone(1).scal, 0, h->zone_len * sizeof(double), st));   // zone of iteration 1
+        S->num_successful_steps = 1; S->num_unsuccessful_steps = 0; S->num_linearizations = 0; S->pcg_iterations_total = 0;
+        S->termination = SSFM_NO_CONVERGENCE;
+        if (fused_publish() && poll && !h->pub_ticket.p) {
+            SSFM_HIP_CHECK(ctx, h->pub_ticket.alloc(1)); SSFM_HIP_CHECK(ctx, hipMemsetAsync(h->pub_ticket.p, 0, sizeof(int), st));
+        }
+        if (phases) for (auto& e : h->phase_ev) if (!e) SSFM_HIP_CHECK(ctx, hipEventCreate(&e));
+#ifdef SSFM_LAB
+        { const int rc = lab_y_probe_alloc(); if (rc) return rc; }
+#endif
+        return SSFM_OK;
+    }
+
+    // ---- the launch sites of the kernels with template variants: one argument list each, the variant chosen by function pointer ----
+    // at = the state it linearises at; scal = the scalar block it adds to; spec = device-side [go, radius] of a speculative launch
+    void point_lin(const State& at, double* scal, const double* spec) {
+        const int PLB = pl_block();
+        LAUNCH(h, KID_POINT_LIN, k_point_lin<3>, (nP + PLB - 1) / PLB, PLB, 0, at.cam, at.rot, at.pts, at.focal, oxy, h->obs_cam.p, h->pt_start.p, nP, h->scale_pt.p,
+               h->scale_f.p, loss, la, radius, O.min_lm_diagonal, O.max_lm_diagonal, h->Vs.p, h->gp.p, scal, spec, lacc);
+    }
+    // finalize + band gather + rhs permutation in one launch
+    void finalize_gather(const ZoneView& z, const NextClear& nc) {
+        const bool merged = F.band_block != DC;                      // 3-dof cameras merged in pairs into 6x6 block rows of the band
+        const auto kernel = merged ? (h->gram_fold ? k_finalize_gather<DC, true, true> : k_finalize_gather<DC, true, false>)
+                                   : (h->gram_fold ? k_finalize_gather<DC, false, true> : k_finalize_gather<DC, false, false>);
+        LAUNCH(h, KID_FINALIZE, kernel, Nc, 256, 0, h->row_ptr.p, h->col_idx.p, h->diag_slot.p, h->scale_cam.p, h->scale_f.p, z.Udiag, z.gcraw,
+               radius, O.min_lm_diagonal, O.max_lm_diagonal, Nc, h->cam_pos.p, h->cam_pos2.p, h->pair_dummy.p, F.y_rows(DC), F.band, z.S_val, z.rhs, z.Sfc, h->Sff.p, h->band.p, h->Yb.p,
+               z.scal, nc.in_finalize, nc.len2, h->col_pos.p, h->wrap_ptr_p(), h->wrap_blk.p, h->wrap_row2.p,
+               z.fold_part, (const int*)nullptr, h->fold_slot_src.p, z.Udiag, z.gcraw, z.Sfc, z.fold_lacc);
+        h->band_filled = true;
+    }
+    // lpp = lanes per point; res: the residual check of the reduced solve rides along as one extra workgroup; skip = the points k_gram_backsub2 took;
+    // fused (lab, SSFM_PUBLISH_FUSED): the last workgroup publishes with this gate instead of a k_publish launch (as measured: without the long accumulators)
+    void point_backsub(int lpp, bool res, const unsigned char* skip, const LmGate* fused, double* spec) {
+        const int PTB = pt_block();
+        const auto kernel = lpp != 2 ? k_point_backsub<DC, 1> : k_point_backsub<DC, 2>;
+        LAUNCH(h, KID_BACKSUB, kernel, (lpp * nP + PTB - 1) / PTB + (res ? 1 : 0), PTB, 0, x.cam, x.rot, x.pts, x.focal, oxy, h->obs_cam.p, h->pt_start.p, nP, h->scale_cam.p,
+               h->scale_pt.p, h->scale_f.p, h->Vs.p, h->gp.p, h->px.p, Nc, loss, la, c.cam, c.rot, c.focal, c.pts, h->scal.p,
+               h->rhs, h->pq.p, h->Sfc, h->Sff.p, O.pcg_tolerance * O.pcg_tolerance, res ? h->pr.p : (double*)nullptr, h->pcg.p, skip,
+               fused ? h->pub_ticket.p : (int*)nullptr, fused ? h->host_pub : (double*)nullptr, fused ? ++ctx->pub_seq : 0ull, fused ? *fused : LmGate(), spec,
+               fused ? (long long*)nullptr : lacc);
+    }
+    // waves per task: a small problem (config 2: 900 tasks on 1024 SIMDs) runs with several waves per SIMD, each with a share of its task's sub-chunks
+    // (config 2, hipEvent: 1 wave per task 26.3 us, 2: 24, 4: 21.1, 6 / 8: 24; k_point_backsub 23.0)
+    void gram_backsub(bool res) {
+        const int ng = (int)(F.gr_rec.size() / GRAM_REC);
+        const int gbs_wave_target = 14 * ctx->num_cus;      // ~3.5 waves per SIMD in flight (config 2: 900 tasks x 4; 1200 tasks x 1 took 31 us, x 3: see profiles/r06_notes.md r06i)
+        const int gbs_split = gbs_split_env > 0 ? std::min(8, gbs_split_env) : std::max(1, std::min(4, (gbs_wave_target + ng - 1) / std::max(1, ng)));
+        LAUNCH(h, KID_GRAM_BACKSUB, k_gram_backsub2<DC>, (ng * gbs_split + GBS_WAVES - 1) / GBS_WAVES + (res ? 1 : 0), 64 * GBS_WAVES, GBS_WAVES * GBS2_TAIL * sizeof(double), x.cam, x.rot, x.pts, x.focal, oxy, ng, h->gr_rec.p,
+               h->scale_cam.p, h->scale_f.p, h->Vs.p, h->px.p, Nc, loss, la, c.cam, c.rot, c.focal, c.pts, h->scal.p,
+               h->rhs, h->pq.p, h->Sfc, h->Sff.p, O.pcg_tolerance * O.pcg_tolerance, res ? h->pr.p : (double*)nullptr, h->pcg.p, lacc, gbs_split);
+    }
+    // the kernel of a tile class (launch_gram)
+    using GramKernel = decltype(&k_schur_gram<DC, 1, 0, false>);
+    template <bool FUSE> static GramKernel gram_kernel_of(int cls) {
+        static const GramKernel k[5] = {k_schur_gram<DC, 1, 0, FUSE>, k_schur_gram<DC, 1, 2, FUSE>, k_schur_gram<DC, 2, 0, FUSE>, k_schur_gram<DC, 2, 3, FUSE>, k_schur_gram<DC, 3, 0, FUSE>};
+        return k[cls];
+    }
+    GramKernel gram_kernel(int cls) const {
+#ifdef SSFM_LAB
+        if (fuse_lin) return gram_kernel_of<true>(cls);
+#endif
+        return gram_kernel_of<false>(cls);
+    }
+    // signature groups: Gram products on the matrix cores (ba_kernels.h: k_schur_gram); one launch per tile class.  at = the state it linearises at,
+    // z = the zone it accumulates into, spec = device-side [go, radius] of a speculative launch (fused point pass only)
+    int launch_gram(const State& at, const ZoneView& z, const double* spec) {
+        const int ng = (int)(F.gr_rec.size() / GRAM_REC);
+        const bool gram_t4 = SSFM_LAB_KNOB("SSFM_GRAM_T4", 1) != 0;
+        const int gram_waves = std::min(4, std::max(1, SSFM_LAB_KNOB("SSFM_GRAM_WAVES", 1)));   // waves (tasks) per workgroup: 1 measured best (2: +14 %, 4: +13 % at the configs[4] size)
+        long long* gram_dbg = nullptr;
+#ifdef SSFM_LAB
+        gram_dbg = lab_gram_stamps_begin(ng);
+#endif
+        // one launch per tile class (the tasks are sorted by K, i.e. by rows = DC K): rows <= 16 -> 1 row tile of 16; 17..20 -> 1 tile + a tail of <= 4 rows through
+        // the 4x4x4 instruction; <= 32 -> 2 tiles; 33..36 -> 2 tiles + tail; else 3 tiles
+        auto tile_class = [&](int K) { const int rows = DC * K; return rows <= 16 ? 0 : (rows <= 20 && gram_t4) ? 1 : rows <= 32 ? 2 : (rows <= 36 && gram_t4) ? 3 : 4; };
+        int cls_end[5] = {0, 0, 0, 0, 0};
+        for (int t = 0; t < ng; t++) { const int c0 = tile_class(F.gr_rec[(size_t)t * GRAM_REC + 2]); for (int cl = c0; cl < 5; cl++) cls_end[cl] = t + 1; }
+        int n_cls = 0; for (int cl = 0; cl < 5; cl++) if (cls_end[cl] > (cl ? cls_end[cl - 1] : 0)) n_cls++;
+        const bool gram_any = F.gram_any;                                 // SSFM_GRAM_ANY as the PLAN read it (one value for the cost model and the launch; 0: one launch per tile class)
+        bool any_ok = gram_any && n_cls > 1 && gram_waves == 1 && !gram_dbg;
+#ifdef SSFM_LAB
+        any_ok = any_ok && !fuse_lin;
+#endif
+        if (any_ok) {
+            // tracks of mixed length: every tile class in ONE launch (ba_kernels.h: k_schur_gram_any), LDS for the largest class
+            const int rows_alloc = DC * F.gr_rec[(size_t)(ng - 1) * GRAM_REC + 2];
+            const size_t gram_lds = ((size_t)rows_alloc * GRAM_LD + GRAM_TAIL) * sizeof(double);
+            if (gram_lds > 48 * 1024) SSFM_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_schur_gram_any<DC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_lds));
+            LAUNCH(h, KID_SCHUR_GRAM, (k_schur_gram_any<DC>), ng, 64, gram_lds, at.cam, at.rot, at.pts, at.focal, oxy, ng, h->gr_rec.p, h->scale_cam.p, h->scale_f.p, h->Vs.p, loss, la, rows_alloc,
+                   F.focal_free ? 1 : 0, gram_t4 ? 1 : 0, z.S_val, z.rhs, z.Udiag, z.Sfc, z.gcraw, z.det);
+        } else {
+            GramFuse fz; fz.scale_pt = h->scale_pt.p; fz.radius = radius; fz.min_diag = O.min_lm_diagonal; fz.max_diag = O.max_lm_diagonal; fz.PS_out = h->Vs.p; fz.gp_out = h->gp.p; fz.scal = z.scal; fz.emit_skip = SSFM_LAB_KNOB("SSFM_GRAM_EMIT_SKIP", 0); fz.spec = spec;
+            for (int cl = 0; cl < (DC == 6 ? 5 : 3); cl++) {              // (3-dof cameras: two row tiles at most)
+                const int t0 = cl ? cls_end[cl - 1] : 0, t1 = cls_end[cl];
+                if (t1 <= t0) continue;
+                const GramKernel kernel = gram_kernel(cl);
+                const int rows_alloc = DC * F.gr_rec[(size_t)(t1 - 1) * GRAM_REC + 2];              // the largest K of the class: its last task
+                const size_t gram_lds = (size_t)gram_waves * ((size_t)rows_alloc * GRAM_LD + GRAM_TAIL) * sizeof(double);
+                if (gram_lds > 48 * 1024) SSFM_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_lds));
+                LAUNCH(h, KID_SCHUR_GRAM, kernel, (t1 - t0 + gram_waves - 1) / gram_waves, 64 * gram_waves, gram_lds, at.cam, at.rot, at.pts, at.focal, oxy, t1, h->gr_rec.p,
+                       h->scale_cam.p, h->scale_f.p, h->Vs.p, loss, la, rows_alloc, F.focal_free ? 1 : 0, t0, z.S_val, z.rhs, z.Udiag, z.Sfc, z.gcraw, gram_dbg, fz, z.det);
+            }
+        }
+#ifdef SSFM_LAB
+        if (gram_dbg) lab_gram_stamps_print(gram_dbg, ng);
+#endif
+        return SSFM_OK;
+    }
+
+    // ================= assemble at x with the current radius =================
+    int assemble() {
         // this iteration's zone (scalars, solver flags, [S | rhs | diag U | S_fc | Jc^T r | sums]) was zeroed behind the previous iteration
         h->set_zone(iteration & 1);
-        if (phases) SSFM_HIP_CHECK(ctx, hipEventRecord(h->phase_ev[0], st));
+        const ZoneView z = zone(iteration);
+        { const int rc = record_phase(0); if (rc) return rc; }
         // per-kernel profiling: the first launch after the host's hand-over would carry the queue's wake-up inside its event bracket (k_point_lin read 25.7 us
         // against 14.7 us under rocprofv3); an empty launch takes that, the bracket of the real kernel then starts behind it like every other one
         if (h->profile && nP > 0 && !lin_done) hipLaunchKernelGGL(k_profile_pad, dim3(1), dim3(64), 0, st);
-        if (nP > 0 && !lin_done && !fuse_lin)             // (lin_done: it ran speculatively behind the previous iteration, with this radius)
-            LAUNCH(h, KID_POINT_LIN, k_point_lin<3>, (nP + PLB - 1) / PLB, PLB, 0, cam_x, rot_x, pts_x, fx, oxy, h->obs_cam.p, h->pt_start.p, nP, h->scale_pt.p,
-                   h->scale_f.p, loss, la, radius, O.min_lm_diagonal, O.max_lm_diagonal, h->Vs.p, h->gp.p, h->scal.p, (const double*)nullptr, lacc);
-        if (phases) SSFM_HIP_CHECK(ctx, hipEventRecord(h->phase_ev[1], st));
+        if (nP > 0 && !lin_done && !fuse_lin) point_lin(x, z.scal, nullptr);      // (lin_done: it ran speculatively behind the previous iteration, with this radius)
+        { const int rc = record_phase(1); if (rc) return rc; }
         if (!F.cs_task_cam.empty()) {
             const int ntasks = (int)F.cs_task_cam.size();
-            LAUNCH(h, KID_CAM_SUMS, k_cam_sums2<DC>, (ntasks + 3) / 4, 256, 0, cam_x, rot_x, pts_x, fx, oxy, h->cam_obs.p, h->cam_obs_pt.p, h->cs_task_cam.p,
-                   h->cs_task_q0.p, h->cs_task_q1.p, ntasks, h->row_ptr.p, h->diag_slot.p, h->scale_cam.p, h->scale_f.p, h->Vs.p, loss, la, h->S_val, h->rhs,
-                   h->Udiag, h->Sfc, h->gcraw, (const unsigned char*)(F.gram_points > 0 ? h->pt_grouped.p : nullptr), det_zone(zone_ptrs(iteration & 1)));
+            LAUNCH(h, KID_CAM_SUMS, k_cam_sums2<DC>, (ntasks + 3) / 4, 256, 0, x.cam, x.rot, x.pts, x.focal, oxy, h->cam_obs.p, h->cam_obs_pt.p, h->cs_task_cam.p,
+                   h->cs_task_q0.p, h->cs_task_q1.p, ntasks, h->row_ptr.p, h->diag_slot.p, h->scale_cam.p, h->scale_f.p, h->Vs.p, loss, la, z.S_val, z.rhs,
+                   z.Udiag, z.Sfc, z.gcraw, (const unsigned char*)(F.gram_points > 0 ? h->pt_grouped.p : nullptr), z.det);
         }
         if (!F.chunk_cam.empty()) {
             const int ntasks = (int)F.chunk_cam.size();
+            auto kernel = k_schur_pairs2<DC>; bool occ3 = false;
 #ifdef SSFM_LAB
-            static const bool occ3 = SSFM_LAB_KNOB("SSFM_PAIRS_OCC3", 0) != 0;      // experiment (ba_kernels.h): three waves per SIMD, slower
-            if (occ3 && DC == 6)
-                LAUNCH(h, KID_SCHUR_ROWS, (k_schur_pairs2<DC, 3>), (ntasks + 3) / 4, 256, 0, cam_x, rot_x, pts_x, fx, oxy, h->row_ptr.p, h->col_idx.p, h->chunk_cam.p,
-                       h->chunk_b0.p, h->chunk_b1.p, ntasks, h->batch_slot.p, h->pair_j.p, h->pair_j2.p, h->pair_p.p, h->scale_cam.p, h->Vs.p, loss, la, h->S_val);
-            else
+            occ3 = SSFM_LAB_KNOB("SSFM_PAIRS_OCC3", 0) != 0 && DC == 6;      // experiment (ba_kernels.h): three waves per SIMD, slower; doubles only
+            if (occ3) kernel = k_schur_pairs2<DC, 3>;
 #endif
-            LAUNCH(h, KID_SCHUR_ROWS, k_schur_pairs2<DC>, (ntasks + 3) / 4, 256, 0, cam_x, rot_x, pts_x, fx, oxy, h->row_ptr.p, h->col_idx.p, h->chunk_cam.p,
-                   h->chunk_b0.p, h->chunk_b1.p, ntasks, h->batch_slot.p, h->pair_j.p, h->pair_j2.p, h->pair_p.p, h->scale_cam.p, h->Vs.p, loss, la, h->S_val,
-                   det_zone(zone_ptrs(iteration & 1)));
+            LAUNCH(h, KID_SCHUR_ROWS, kernel, (ntasks + 3) / 4, 256, 0, x.cam, x.rot, x.pts, x.focal, oxy, h->row_ptr.p, h->col_idx.p, h->chunk_cam.p,
+                   h->chunk_b0.p, h->chunk_b1.p, ntasks, h->batch_slot.p, h->pair_j.p, h->pair_j2.p, h->pair_p.p, h->scale_cam.p, h->Vs.p, loss, la, z.S_val,
+                   occ3 ? DetZone{} : z.det);
         }
-        // signature groups: Gram products on the matrix cores (ba_kernels.h: k_schur_gram); one launch per tile class.  xc / xr / xp / xf = the state it linearises at,
-        // z = the zone it accumulates into, spec = device-side [go, radius] of a speculative launch (fused point pass only)
-        auto launch_gram = [&](const double* xc, const double* xr, const double* xp, const double* xf, const ZonePtrs& z, double rad, const double* spec) -> int {
-            const int ng = (int)(F.gr_rec.size() / GRAM_REC);
-            static bool gram_stamps_done = SSFM_LAB_KNOB("SSFM_GRAM_STAMPS", 0) == 0;      // timing study: per-task phase stamps of the first launch
-            long long* gram_dbg = nullptr;
-            if (!gram_stamps_done) (void)hipMalloc((void**)&gram_dbg, (size_t)4 * ng * sizeof(long long));
-            static const bool gram_t4 = SSFM_LAB_KNOB("SSFM_GRAM_T4", 1) != 0;
-            static const int gram_waves = std::min(4, std::max(1, SSFM_LAB_KNOB("SSFM_GRAM_WAVES", 1)));   // waves (tasks) per workgroup: 1 measured best (2: +14 %, 4: +13 % at the configs[4] size)
-            // one launch per tile class (the tasks are sorted by K, i.e. by rows = DC K): rows <= 16 -> 1 row tile of 16; 17..20 -> 1 tile + a tail of <= 4 rows through
-            // the 4x4x4 instruction; <= 32 -> 2 tiles; 33..36 -> 2 tiles + tail; else 3 tiles
-            auto tile_class = [&](int K) { const int rows = DC * K; return rows <= 16 ? 0 : (rows <= 20 && gram_t4) ? 1 : rows <= 32 ? 2 : (rows <= 36 && gram_t4) ? 3 : 4; };
-            int cls_end[5] = {0, 0, 0, 0, 0};
-            for (int t = 0; t < ng; t++) { const int c0 = tile_class(F.gr_rec[(size_t)t * GRAM_REC + 2]); for (int c = c0; c < 5; c++) cls_end[c] = t + 1; }
-            GramFuse fz; fz.scale_pt = h->scale_pt.p; fz.radius = rad; fz.min_diag = O.min_lm_diagonal; fz.max_diag = O.max_lm_diagonal; fz.PS_out = h->Vs.p; fz.gp_out = h->gp.p; fz.scal = z.scal; fz.emit_skip = SSFM_LAB_KNOB("SSFM_GRAM_EMIT_SKIP", 0); fz.spec = spec;
-#define SSFM_GRAM_LAUNCH_(CLS_, NT_, TI_, FUSE_)                                                                                                       \
-            do {                                                                                                                                       \
-                const int t0 = (CLS_ == 0) ? 0 : cls_end[(CLS_ >= 1) ? CLS_ - 1 : 0], t1 = cls_end[CLS_];                                             \
-                if (t1 > t0) {                                                                                                                         \
-                    const int rows_alloc = DC * F.gr_rec[(size_t)(t1 - 1) * GRAM_REC + 2];              /* the largest K of the class: its last task */ \
-                    const size_t gram_lds = (size_t)gram_waves * ((size_t)rows_alloc * GRAM_LD + GRAM_TAIL) * sizeof(double);                          \
-                    if (gram_lds > 48 * 1024)                                                                                                          \
-                        SSFM_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_schur_gram<DC, NT_, TI_, FUSE_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_lds)); \
-                    LAUNCH(h, KID_SCHUR_GRAM, (k_schur_gram<DC, NT_, TI_, FUSE_>), (t1 - t0 + gram_waves - 1) / gram_waves, 64 * gram_waves, gram_lds, xc, xr, xp, xf, oxy, t1, h->gr_rec.p,  \
-                           h->scale_cam.p, h->scale_f.p, h->Vs.p, loss, la, rows_alloc, F.focal_free ? 1 : 0, t0, z.S_val, z.rhs, z.Udiag, z.Sfc, z.gcraw, gram_dbg, fz, det_zone(z));  \
-                }                                                                                                                                      \
-            } while (0)
-#ifdef SSFM_LAB
-#define SSFM_GRAM_LAUNCH(CLS_, NT_, TI_) do { if (fuse_lin) SSFM_GRAM_LAUNCH_(CLS_, NT_, TI_, true); else SSFM_GRAM_LAUNCH_(CLS_, NT_, TI_, false); } while (0)
-#else
-#define SSFM_GRAM_LAUNCH(CLS_, NT_, TI_) SSFM_GRAM_LAUNCH_(CLS_, NT_, TI_, false)
-#endif
-            int n_cls = 0; for (int c = 0; c < 5; c++) if (cls_end[c] > (c ? cls_end[c - 1] : 0)) n_cls++;
-            const bool gram_any = F.gram_any;                                 // SSFM_GRAM_ANY as the PLAN read it (one value for the cost model and the launch; 0: one launch per tile class)
-            bool any_ok = gram_any && n_cls > 1 && gram_waves == 1 && !gram_dbg;
-#ifdef SSFM_LAB
-            any_ok = any_ok && !fuse_lin;
-#endif
-            if (any_ok) {
-                // tracks of mixed length: every tile class in ONE launch (ba_kernels.h: k_schur_gram_any), LDS for the largest class
-                const int rows_alloc = DC * F.gr_rec[(size_t)(ng - 1) * GRAM_REC + 2];
-                const size_t gram_lds = ((size_t)rows_alloc * GRAM_LD + GRAM_TAIL) * sizeof(double);
-                if (gram_lds > 48 * 1024) SSFM_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_schur_gram_any<DC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_lds));
-                LAUNCH(h, KID_SCHUR_GRAM, (k_schur_gram_any<DC>), ng, 64, gram_lds, xc, xr, xp, xf, oxy, ng, h->gr_rec.p, h->scale_cam.p, h->scale_f.p, h->Vs.p, loss, la, rows_alloc,
-                       F.focal_free ? 1 : 0, gram_t4 ? 1 : 0, z.S_val, z.rhs, z.Udiag, z.Sfc, z.gcraw, det_zone(z));
-            } else {
-                SSFM_GRAM_LAUNCH(0, 1, 0); SSFM_GRAM_LAUNCH(1, 1, 2); SSFM_GRAM_LAUNCH(2, 2, 0);
-                if (DC == 6) { SSFM_GRAM_LAUNCH(3, 2, 3); SSFM_GRAM_LAUNCH(4, 3, 0); }
-            }
-#undef SSFM_GRAM_LAUNCH
-#undef SSFM_GRAM_LAUNCH_
-            if (gram_dbg) {                                        // print the phase times of this launch (100 MHz clock) and stop stamping
-                std::vector<long long> st2((size_t)4 * ng); (void)hipStreamSynchronize(h->ctx->stream); (void)hipMemcpy(st2.data(), gram_dbg, st2.size() * sizeof(long long), hipMemcpyDeviceToHost);
-                long long tmin = st2[0], tmax = 0; double a = 0, b = 0, c = 0;
-                for (int t = 0; t < ng; t++) { tmin = std::min(tmin, st2[4 * t]); tmax = std::max(tmax, st2[4 * t + 3]); a += st2[4 * t + 1] - st2[4 * t]; b += st2[4 * t + 2] - st2[4 * t + 1]; c += st2[4 * t + 3] - st2[4 * t + 2]; }
-                std::fprintf(stderr, "[gram] %d tasks, kernel span %.1f us; mean per task: start + first linearisation %.2f us, tiles + other sub-chunks %.2f us, emission %.2f us\n", ng, (tmax - tmin) * 0.01,
-                             a / ng * 0.01, b / ng * 0.01, c / ng * 0.01);
-                { double s_mean = 0, s_max = 0, e_mean = 0, a_max = 0, b_max = 0, c_max = 0;
-                  for (int t = 0; t < ng; t++) { const double so = (st2[4 * t] - tmin) * 0.01; s_mean += so; s_max = std::max(s_max, so); e_mean += (st2[4 * t + 3] - tmin) * 0.01;
-                                                 a_max = std::max(a_max, (st2[4 * t + 1] - st2[4 * t]) * 0.01); b_max = std::max(b_max, (st2[4 * t + 2] - st2[4 * t + 1]) * 0.01); c_max = std::max(c_max, (st2[4 * t + 3] - st2[4 * t + 2]) * 0.01); }
-                  std::fprintf(stderr, "[gram] task start after the first: mean %.2f max %.2f us; task end mean %.2f us; longest phases %.2f | %.2f | %.2f us\n", s_mean / ng, s_max, e_mean / ng, a_max, b_max, c_max); }
-                (void)hipFree(gram_dbg); gram_dbg = nullptr; gram_stamps_done = true;
-            }
-            return SSFM_OK;
-        };
         if (!F.gr_rec.empty() && !(fuse_lin && lin_done)) {          // (fused + lin_done: the whole assembly of this iteration ran speculatively behind the previous one)
-            const int rc = launch_gram(cam_x, rot_x, pts_x, fx, zone_ptrs(iteration & 1), radius, nullptr); if (rc) return rc;
+            const int rc = launch_gram(x, z, nullptr); if (rc) return rc;
         }
         lin_done = false;
 #ifdef SSFM_LAB
-        if (y_probe && !F.chunk_cam.empty()) {                     // experiment only (ba_kernels.h: k_pairs_y_probe)
-            const int ntasks = (int)F.chunk_cam.size();
-            hipLaunchKernelGGL(k_pairs_y_probe<DC>, dim3((ntasks + 3) / 4), dim3(256), 0, st, h->row_ptr.p, h->col_idx.p, h->chunk_cam.p, h->chunk_b0.p, h->chunk_b1.p, ntasks,
-                               h->batch_slot.p, h->pair_j.p, h->pair_j2.p, h->scale_cam.p, probe_Y.p, probe_S.p);
-        }
+        lab_y_probe_launch();
 #endif
         if (h->det && !h->gram_fold) {
-            det_decode(zone_ptrs(iteration & 1), true, DET_K_ASSEMBLY);      // limbs -> the zone's doubles (and cleared); the point pass's sums -> replica 0 of the scalar block
+            det_decode(z, true, DET_K_ASSEMBLY);      // limbs -> the zone's doubles (and cleared); the point pass's sums -> replica 0 of the scalar block
             SSFM_HIP_CHECK(ctx, hipMemsetAsync(h->det_limb.p, 0, sizeof(long long), st));      // the poison word: read by every decode workgroup, cleared behind the launch
         }
         // (atomics-free emission, gram_fold: nothing went through the limbs; the focal sums are folded from the long accumulators by k_finalize_gather, the cost by k_publish:
@@ -283,161 +356,115 @@ static int lm_loop(ssfm_ba_handle* h, ssfm_ba_summary* S) {
             int rc = allreduce(h, h->redbuf.p, (size_t)h->n_red, ncclSum); if (rc) return rc;
             hipLaunchKernelGGL(k_scal_unpack, dim3(1), dim3(64), 0, st, h->scal.p, h->red_scal, ctx->nranks);
         }
-        // the next iteration's zone is cleared by the finalize kernel (a slice per workgroup) when its length allows 16-byte stores
-        double* next_zone = h->zone.p + (size_t)((iteration + 1) & 1) * h->zone_len;
-        const bool clear_in_finalize = O.preconditioner == 0 && zone_clear_fused && (h->zone_len % 2 == 0) && ((reinterpret_cast<uintptr_t>(next_zone) & 15) == 0);
-        double2* clear_next = clear_in_finalize ? reinterpret_cast<double2*>(next_zone) : (double2*)nullptr;
-        const size_t clear_len2 = clear_in_finalize ? h->zone_len / 2 : 0;
-        const double* fold_part = h->gram_fold ? h->gram_part.p : (const double*)nullptr;      // atomics-free Gram emission: k_finalize_gather folds the tasks' partial blocks first
-        if (O.preconditioner == 0) {                               // finalize + band gather + rhs permutation in one launch
-            if (F.band_block != DC)      // 3-dof cameras merged in pairs into 6x6 block rows of the band
-                { if (h->gram_fold) LAUNCH(h, KID_FINALIZE, (k_finalize_gather<DC, true, true>), Nc, 256, 0, h->row_ptr.p, h->col_idx.p, h->diag_slot.p, h->scale_cam.p, h->scale_f.p, h->Udiag, h->gcraw,
-                       radius, O.min_lm_diagonal, O.max_lm_diagonal, Nc, h->cam_pos.p, h->cam_pos2.p, h->pair_dummy.p, F.y_rows(DC), F.band, h->S_val, h->rhs, h->Sfc, h->Sff.p, h->band.p, h->Yb.p, h->scal.p, clear_next, clear_len2, h->col_pos.p, h->wrap_ptr_p(), h->wrap_blk.p, h->wrap_row2.p,
-                       fold_part, (const int*)nullptr, h->fold_slot_src.p, h->Udiag, h->gcraw, h->Sfc, h->gram_fold ? lacc : (long long*)nullptr); else LAUNCH(h, KID_FINALIZE, (k_finalize_gather<DC, true>), Nc, 256, 0, h->row_ptr.p, h->col_idx.p, h->diag_slot.p, h->scale_cam.p, h->scale_f.p, h->Udiag, h->gcraw,
-                       radius, O.min_lm_diagonal, O.max_lm_diagonal, Nc, h->cam_pos.p, h->cam_pos2.p, h->pair_dummy.p, F.y_rows(DC), F.band, h->S_val, h->rhs, h->Sfc, h->Sff.p, h->band.p, h->Yb.p, h->scal.p, clear_next, clear_len2, h->col_pos.p, h->wrap_ptr_p(), h->wrap_blk.p, h->wrap_row2.p,
-                       fold_part, (const int*)nullptr, h->fold_slot_src.p, h->Udiag, h->gcraw, h->Sfc, h->gram_fold ? lacc : (long long*)nullptr); }
-            else
-                { if (h->gram_fold) LAUNCH(h, KID_FINALIZE, (k_finalize_gather<DC, false, true>), Nc, 256, 0, h->row_ptr.p, h->col_idx.p, h->diag_slot.p, h->scale_cam.p, h->scale_f.p, h->Udiag, h->gcraw,
-                       radius, O.min_lm_diagonal, O.max_lm_diagonal, Nc, h->cam_pos.p, h->cam_pos2.p, h->pair_dummy.p, F.y_rows(DC), F.band, h->S_val, h->rhs, h->Sfc, h->Sff.p, h->band.p, h->Yb.p, h->scal.p, clear_next, clear_len2, h->col_pos.p, h->wrap_ptr_p(), h->wrap_blk.p, h->wrap_row2.p,
-                       fold_part, (const int*)nullptr, h->fold_slot_src.p, h->Udiag, h->gcraw, h->Sfc, h->gram_fold ? lacc : (long long*)nullptr); else LAUNCH(h, KID_FINALIZE, (k_finalize_gather<DC, false>), Nc, 256, 0, h->row_ptr.p, h->col_idx.p, h->diag_slot.p, h->scale_cam.p, h->scale_f.p, h->Udiag, h->gcraw,
-                       radius, O.min_lm_diagonal, O.max_lm_diagonal, Nc, h->cam_pos.p, h->cam_pos2.p, h->pair_dummy.p, F.y_rows(DC), F.band, h->S_val, h->rhs, h->Sfc, h->Sff.p, h->band.p, h->Yb.p, h->scal.p, clear_next, clear_len2, h->col_pos.p, h->wrap_ptr_p(), h->wrap_blk.p, h->wrap_row2.p,
-                       fold_part, (const int*)nullptr, h->fold_slot_src.p, h->Udiag, h->gcraw, h->Sfc, h->gram_fold ? lacc : (long long*)nullptr); }
-            h->band_filled = true;
-        } else {
-            LAUNCH(h, KID_FINALIZE, k_finalize_S<DC>, gp_cam, 64, 0, h->row_ptr.p, h->diag_slot.p, h->scale_cam.p, h->scale_f.p, h->Udiag, h->gcraw,
-                   radius, O.min_lm_diagonal, O.max_lm_diagonal, Nc, h->S_val, h->Minv.p, h->rhs, h->Sff.p, h->scal.p);
+        if (O.preconditioner == 0) finalize_gather(z, next_clear());
+        else LAUNCH(h, KID_FINALIZE, k_finalize_S<DC>, gp_cam, 64, 0, h->row_ptr.p, h->diag_slot.p, h->scale_cam.p, h->scale_f.p, z.Udiag, z.gcraw,
+                    radius, O.min_lm_diagonal, O.max_lm_diagonal, Nc, z.S_val, h->Minv.p, z.rhs, h->Sff.p, z.scal);
+        return record_phase(2);
+    }
+
+    // ================= solve the reduced system, then step / candidate / model cost / candidate cost =================
+    // The direct solve and the tail are enqueued back to back; the solver's residual flags come back with the
+    // iteration scalars in ONE host synchronisation.  Only if the residual test failed (rare) does PCG refinement
+    // run and the tail get redone (refine_if_needed).
+    int solve() {
+        pcg_iters = 0; pcg_ok = false;
+        h->tail.on = fused_cams; h->tail.residual_later = residual_later; h->tail.cam = x.cam; h->tail.focal = x.focal; h->tail.cam_c = c.cam; h->tail.focal_c = c.focal; h->tail.rot_c = c.rot;
+        const int rc = solve_reduced<DC>(h, host_pcg1, &pcg_iters, &pcg_ok, 0); h->tail.on = false; h->tail.residual_later = false; if (rc) return rc;
+        return record_phase(3);
+    }
+    // the device-side gate of the hand-over ("accepted, go on" + the next radius, by the rules of decide) and when a speculative launch may follow it
+    LmGate gate() const {
+        LmGate g; g.enabled = 1; g.last_successful = last_successful ? 1 : 0; g.radius = radius; g.x_norm = x_norm;
+        g.function_tolerance = O.function_tolerance; g.gradient_tolerance = O.gradient_tolerance; g.parameter_tolerance = O.parameter_tolerance;
+        g.min_relative_decrease = O.min_relative_decrease; g.max_radius = O.max_trust_region_radius; g.min_radius = O.min_trust_region_radius;
+        return g;
+    }
+    bool may_speculate(bool with_cams) const { return spec_on && !with_cams && !(h->profile || O.verbose) && iteration < O.max_num_iterations; }
+    // per point: back-substitution, candidate, model cost change, candidate cost.  res: the residual check of the reduced solve rides along
+    void back_substitute(bool res) {
+        // the points of signature groups take k_gram_backsub (lane = observation, camera records in LDS); k_point_backsub keeps the others and
+        // the residual check's extra workgroup
+        // Its time follows the POINTS (8 lanes per point whatever K), k_point_backsub's the observations: measured (rounds 3-5, k_gram_backsub) 27.3 / 28.1 us
+        // at K = 6 / 8 against 23.4 / 31.7 (100k points) and 271 / 278 against 284 / 379 (1.5 M points).  Round 6, k_gram_backsub2: 195 us at 1.5 M points (K = 8),
+        // 21.1 against 23.0 us at config 2 (K = 6, four waves per task): on from 6 observations per point on average.
+        // SSFM_GRAM_BACKSUB=0 / 1 forces it off / on.
+        const bool grouped = !fused_publish() && !F.gr_rec.empty() && (gram_bs < 0 ? F.gram_obs >= 6 * F.gram_points : gram_bs != 0);
+        const bool all_grouped = grouped && F.gram_points == F.nP;               // then the residual check's workgroup rides with k_gram_backsub
+        if (grouped) gram_backsub(res && all_grouped);
+        if (all_grouped) return;
+        // EXPERIMENT, off (SSFM_BACKSUB_LPP=2): two lanes per point -- half the dependent camera gathers per lane, twice the waves.  Measured at config 2
+        // (scripts/lab/ab_lpp.sh, hipEvent averages): 25.1-25.3 us against 23.0-23.5 with one lane per point; 2.557 against 2.538-2.552 ms per solve
+        // r05ai: on LONG tracks it pays -- 300 cameras, tracks of 3 ... 14 (8.5 observations per point, 70 000 points = one wave per SIMD): 40.1 -> 33.0 us;
+        // tracks 3 ... 8 (5.5 per point): 26.7 -> 28.7.  Two lanes per point from 8.25 observations per point on.
+        const int bs_lpp_env = SSFM_LAB_KNOB("SSFM_BACKSUB_LPP", 0);
+        const int bs_lpp = bs_lpp_env > 0 ? bs_lpp_env : ((int64_t)4 * F.M > (int64_t)33 * F.nP ? 2 : 1);
+        point_backsub(bs_lpp == 2 ? 2 : 1, res, grouped ? h->pt_grouped.p : (const unsigned char*)nullptr, nullptr, nullptr);
+    }
+    // candidate cameras + their rotation tables (with_cams; otherwise the solve's arrow kernel wrote them), the points' tail, the hand-over
+    int enqueue_tail(bool with_cams) {
+        { const int rc = need_x0(); if (rc) return rc; }
+        if (with_cams) {
+            LAUNCH(h, KID_CAM_UPDATE, k_cam_update<DC>, 1, 1024, 0, x.cam, x.focal, h->scale_cam.p, h->scale_f.p, h->px.p, Nc, c.cam, c.focal, c.rot, h->scal.p, Nc <= 1024 ? 1 : 0);
+            if (Nc > 1024) LAUNCH(h, KID_CAM_ROT, k_cam_rot, gp_cam, 64, 0, c.cam, c.rot, Nc);
         }
-        if (phases) SSFM_HIP_CHECK(ctx, hipEventRecord(h->phase_ev[2], st));
-        // ================= solve the reduced system, then step / candidate / model cost / candidate cost =================
-        // The direct solve and the tail are enqueued back to back; the solver's residual flags come back with the
-        // iteration scalars in ONE host synchronisation.  Only if the residual test failed (rare) does PCG refinement
-        // run and the tail get redone.
-        int pcg_iters = 0; bool pcg_ok = false;
-        // with the banded factor and the lower-triangle storage the arrow kernel of the solve also writes the candidate cameras
-        const bool fused_cams = O.preconditioner == 0 && F.sym_lower;
-        const bool residual_later = fused_cams && nP > 0;
-        h->tail.on = fused_cams; h->tail.residual_later = residual_later; h->tail.cam = cam_x; h->tail.focal = fx; h->tail.cam_c = cam_c; h->tail.focal_c = fc; h->tail.rot_c = rot_c;
-        { int rc = solve_reduced<DC>(h, host_pcg1, &pcg_iters, &pcg_ok, 0); h->tail.on = false; h->tail.residual_later = false; if (rc) return rc; }
-        if (phases) SSFM_HIP_CHECK(ctx, hipEventRecord(h->phase_ev[3], st));
-        auto enqueue_tail = [&](bool with_cams) -> int {
-            { const int rc0 = need_x0(); if (rc0) return rc0; }
-            // candidate cameras + their rotation tables; then per point: back-substitution, candidate, model cost change, candidate cost
-            if (with_cams) {
-                LAUNCH(h, KID_CAM_UPDATE, k_cam_update<DC>, 1, 1024, 0, cam_x, fx, h->scale_cam.p, h->scale_f.p, h->px.p, Nc, cam_c, fc, rot_c, h->scal.p, Nc <= 1024 ? 1 : 0);
-                if (Nc > 1024) LAUNCH(h, KID_CAM_ROT, k_cam_rot, gp_cam, 64, 0, cam_c, rot_c, Nc);
-            }
-            bool published = false;
-            if (nP > 0) {
-                const bool res = !with_cams && residual_later;      // first pass of the iteration: the residual check rides along
-                // hand-over fused into this launch (its last workgroup publishes): single rank, polling hand-over, first pass of the iteration
-                const bool fuse_pub = fused_publish && poll && !ctx->collective && res && h->pub_ticket.p;
-                if (fuse_pub) {
-                    LmGate g; std::memset(&g, 0, sizeof(g)); double* specp = nullptr;
-                    spec_launched = false;
-                    if (spec_on && !(h->profile || O.verbose) && iteration < O.max_num_iterations) {
-                        g.enabled = 1; g.last_successful = last_successful ? 1 : 0; g.radius = radius; g.x_norm = x_norm;
-                        g.function_tolerance = O.function_tolerance; g.gradient_tolerance = O.gradient_tolerance; g.parameter_tolerance = O.parameter_tolerance;
-                        g.min_relative_decrease = O.min_relative_decrease; g.max_radius = O.max_trust_region_radius; g.min_radius = O.min_trust_region_radius;
-                        specp = h->lmdev.p; spec_launched = true;
-                    }
-                    LAUNCH(h, KID_BACKSUB, k_point_backsub<DC>, gp_pts_lm + 1, PTB, 0, cam_x, rot_x, pts_x, fx, oxy, h->obs_cam.p, h->pt_start.p, nP, h->scale_cam.p,
-                           h->scale_pt.p, h->scale_f.p, h->Vs.p, h->gp.p, h->px.p, Nc, loss, la, cam_c, rot_c, fc, pts_c, h->scal.p,
-                           h->rhs, h->pq.p, h->Sfc, h->Sff.p, O.pcg_tolerance * O.pcg_tolerance, h->pr.p, h->pcg.p, (const unsigned char*)nullptr,
-                           h->pub_ticket.p, h->host_pub, ++ctx->pub_seq, g, specp);
-                    published = true;
-                } else {
-                    // the points of signature groups take k_gram_backsub (lane = observation, camera records in LDS); k_point_backsub keeps the others and
-                    // the residual check's extra workgroup
-                    // Its time follows the POINTS (8 lanes per point whatever K), k_point_backsub's the observations: measured (rounds 3-5, k_gram_backsub) 27.3 / 28.1 us
-                    // at K = 6 / 8 against 23.4 / 31.7 (100k points) and 271 / 278 against 284 / 379 (1.5 M points).  Round 6, k_gram_backsub2: 195 us at 1.5 M points (K = 8),
-                    // 21.1 against 23.0 us at config 2 (K = 6, four waves per task): on from 6 observations per point on average.
-                    // SSFM_GRAM_BACKSUB=0 / 1 forces it off / on.
-                    const int gram_bs = gram_bs_env;
-                    const bool grouped = !fused_publish && !F.gr_rec.empty() && (gram_bs < 0 ? F.gram_obs >= 6 * F.gram_points : gram_bs != 0);
-                    const bool all_grouped = grouped && F.gram_points == F.nP;               // then the residual check's workgroup rides with k_gram_backsub
-                    if (grouped) {
-                        const int ng = (int)(F.gr_rec.size() / GRAM_REC);
-                        const bool res_here = res && all_grouped;
-                        // waves per task: a small problem (config 2: 900 tasks on 1024 SIMDs) runs with several waves per SIMD, each with a share of its task's sub-chunks
-                        // (config 2, hipEvent: 1 wave per task 26.3 us, 2: 24, 4: 21.1, 6 / 8: 24; k_point_backsub 23.0)
-                        const int gbs_split_env = std::getenv("SSFM_GBS_SPLIT") ? std::atoi(std::getenv("SSFM_GBS_SPLIT")) : 0;      // (read per launch: tests switch it)
-                        const int gbs_wave_target = 14 * ctx->num_cus;      // ~3.5 waves per SIMD in flight (config 2: 900 tasks x 4; 1200 tasks x 1 took 31 us, x 3: see profiles/r06_notes.md r06i)
-                        const int gbs_split = gbs_split_env > 0 ? std::min(8, gbs_split_env) : std::max(1, std::min(4, (gbs_wave_target + ng - 1) / std::max(1, ng)));
-                        LAUNCH(h, KID_GRAM_BACKSUB, k_gram_backsub2<DC>, (ng * gbs_split + GBS_WAVES - 1) / GBS_WAVES + (res_here ? 1 : 0), 64 * GBS_WAVES, GBS_WAVES * GBS2_TAIL * sizeof(double), cam_x, rot_x, pts_x, fx, oxy, ng, h->gr_rec.p,
-                               h->scale_cam.p, h->scale_f.p, h->Vs.p, h->px.p, Nc, loss, la, cam_c, rot_c, fc, pts_c, h->scal.p,
-                               h->rhs, h->pq.p, h->Sfc, h->Sff.p, O.pcg_tolerance * O.pcg_tolerance, res_here ? h->pr.p : (double*)nullptr, h->pcg.p, lacc, gbs_split);
-                    }
-                    // EXPERIMENT, off (SSFM_BACKSUB_LPP=2): two lanes per point -- half the dependent camera gathers per lane, twice the waves.  Measured at config 2
-                    // (scripts/lab/ab_lpp.sh, hipEvent averages): 25.1-25.3 us against 23.0-23.5 with one lane per point; 2.557 against 2.538-2.552 ms per solve
-                    // r05ai: on LONG tracks it pays -- 300 cameras, tracks of 3 ... 14 (8.5 observations per point, 70 000 points = one wave per SIMD): 40.1 -> 33.0 us;
-                    // tracks 3 ... 8 (5.5 per point): 26.7 -> 28.7.  Two lanes per point from 8.25 observations per point on.
-                    static const int bs_lpp_env = SSFM_LAB_KNOB("SSFM_BACKSUB_LPP", 0);
-                    const int bs_lpp = bs_lpp_env > 0 ? bs_lpp_env : ((int64_t)4 * F.M > (int64_t)33 * F.nP ? 2 : 1);
-                    if (!all_grouped && bs_lpp == 2)
-                        LAUNCH(h, KID_BACKSUB, (k_point_backsub<DC, 2>), (2 * nP + PTB - 1) / PTB + (res ? 1 : 0), PTB, 0, cam_x, rot_x, pts_x, fx, oxy, h->obs_cam.p, h->pt_start.p, nP, h->scale_cam.p,
-                               h->scale_pt.p, h->scale_f.p, h->Vs.p, h->gp.p, h->px.p, Nc, loss, la, cam_c, rot_c, fc, pts_c, h->scal.p,
-                               h->rhs, h->pq.p, h->Sfc, h->Sff.p, O.pcg_tolerance * O.pcg_tolerance, res ? h->pr.p : (double*)nullptr, h->pcg.p,
-                               (const unsigned char*)(grouped ? h->pt_grouped.p : nullptr), (int*)nullptr, (double*)nullptr, 0ull, LmGate(), (double*)nullptr, lacc);
-                    else if (!all_grouped)
-                        LAUNCH(h, KID_BACKSUB, k_point_backsub<DC>, gp_pts_lm + (res ? 1 : 0), PTB, 0, cam_x, rot_x, pts_x, fx, oxy, h->obs_cam.p, h->pt_start.p, nP, h->scale_cam.p,
-                               h->scale_pt.p, h->scale_f.p, h->Vs.p, h->gp.p, h->px.p, Nc, loss, la, cam_c, rot_c, fc, pts_c, h->scal.p,
-                               h->rhs, h->pq.p, h->Sfc, h->Sff.p, O.pcg_tolerance * O.pcg_tolerance, res ? h->pr.p : (double*)nullptr, h->pcg.p,
-                               (const unsigned char*)(grouped ? h->pt_grouped.p : nullptr), (int*)nullptr, (double*)nullptr, 0ull, LmGate(), (double*)nullptr, lacc);
-                }
-            }
-            if (published) return SSFM_OK;
-            // deterministic mode: the tail's sums (model change, step and candidate norms, candidate cost) sit in the long accumulators; k_publish folds them itself,
-            // the copying hand-over needs them as doubles in replica 0 first
-            // (with_cams: k_cam_update, one workgroup, has STORED the two camera norms in replica 0 -- they are not in the long accumulators)
-            const unsigned det_kt = (with_cams ? (DET_K_TAIL & ~((1u << SC_STEP2_CAM) | (1u << SC_XN2_CAM))) : DET_K_TAIL) | (h->gram_fold ? (1u << SC_COST) : 0u);   // (gram_fold: the cost was not decoded behind the assembly)
-            if (h->det && !poll) det_decode(zone_ptrs(iteration & 1), false, det_kt);
-            if (ctx->collective) hipLaunchKernelGGL(k_scal_fold, dim3(1), dim3(SC_TOTAL * 64), 0, st, h->scal.p, (double*)nullptr, 0);
-            int rc = allreduce(h, h->scal.p + SC_MODEL, 4, ncclSum); if (rc) return rc;   // MODEL, STEP2_PT, XN2_PT, CAND_COST
-            if (poll) {
-                spec_launched = false;
-                if (spec_on && !with_cams && !(h->profile || O.verbose) && iteration < O.max_num_iterations) {
-                    LmGate g; g.enabled = 1; g.last_successful = last_successful ? 1 : 0; g.radius = radius; g.x_norm = x_norm;
-                    g.function_tolerance = O.function_tolerance; g.gradient_tolerance = O.gradient_tolerance; g.parameter_tolerance = O.parameter_tolerance;
-                    g.min_relative_decrease = O.min_relative_decrease; g.max_radius = O.max_trust_region_radius; g.min_radius = O.min_trust_region_radius;
-                    publish(h, &g, h->lmdev.p, det_kt); spec_launched = true;
-                } else publish(h, nullptr, nullptr, det_kt);
+        if (nP > 0) {
+            const bool res = !with_cams && residual_later;      // first pass of the iteration: the residual check rides along
+            // (lab) hand-over fused into the launch (its last workgroup publishes): single rank, polling hand-over, first pass of the iteration
+            if (fused_publish() && poll && !ctx->collective && res && h->pub_ticket.p) {
+                spec_launched = may_speculate(with_cams);
+                LmGate g; std::memset(&g, 0, sizeof(g)); if (spec_launched) g = gate();
+                point_backsub(1, true, nullptr, &g, spec_launched ? h->lmdev.p : (double*)nullptr);
                 return SSFM_OK;
             }
-            hipError_t e = hipMemcpyAsync(host_sp, h->scal.p, (SC_NSLOT * SC_TOTAL + PCG_TOTAL + 1) * sizeof(double), hipMemcpyDeviceToHost, st);   // scalars + solver flags
-            if (e != hipSuccess) return fail(ctx, SSFM_ERR_HIP, hipGetErrorString(e));
-            return SSFM_OK;
-        };
-        { int rc = enqueue_tail(!fused_cams); if (rc) return rc; }
-        if (phases) SSFM_HIP_CHECK(ctx, hipEventRecord(h->phase_ev[4], st));
-        // (otherwise) the next iteration's zone is cleared while the host wakes up and decides
-        if (!clear_in_finalize) SSFM_HIP_CHECK(ctx, hipMemsetAsync(next_zone, 0, h->zone_len * sizeof(double), st));
-        if (spec_launched && fuse_lin) { const int rc = launch_gram(cam_c, rot_c, pts_c, fc, zone_ptrs((iteration + 1) & 1), radius, (const double*)h->lmdev.p); if (rc) return rc; }
-        else if (spec_launched)              // x = this iteration's candidate, scalars into the next zone (scal is its first block)
-            LAUNCH(h, KID_POINT_LIN, k_point_lin<3>, (nP + PLB - 1) / PLB, PLB, 0, cam_c, rot_c, pts_c, fc, oxy, h->obs_cam.p, h->pt_start.p, nP, h->scale_pt.p,
-                   h->scale_f.p, loss, la, radius, O.min_lm_diagonal, O.max_lm_diagonal, h->Vs.p, h->gp.p, next_zone, (const double*)h->lmdev.p, lacc);
-        { int rc = wait_iteration(); if (rc) return rc; }
-        // what the device decided for the speculative k_point_lin (it ran iff dev_go)
-        const bool dev_go = spec_launched && h->host_pub[SC_TOTAL + PCG_TOTAL + 2] == 1.0;
-        const double dev_radius = spec_launched ? h->host_pub[SC_TOTAL + PCG_TOTAL + 3] : 0.0;
-        auto undo_speculation = [&]() -> int {                       // the host goes another way: the next zone must be clean again
-            if (dev_go) SSFM_HIP_CHECK(ctx, hipMemsetAsync(next_zone, 0, h->zone_len * sizeof(double), st));
-            if (dev_go && h->det) SSFM_HIP_CHECK(ctx, hipMemsetAsync(h->det_lacc.p, 0, (size_t)SC_NSLOT * SC_TOTAL * LA_STRIDE * sizeof(long long), st));   // the speculative point pass's sums
-            return SSFM_OK;
-        };
-        SSFM_HIP_CHECK(ctx, hipGetLastError());                      // a launch that was refused (bad configuration) must not pass silently
-        if (!poll) fold_host_scal();
-        if (O.preconditioner == 0) {
-            int fail_flag; std::memcpy(&fail_flag, &host_pcg1[PCG_TOTAL], sizeof(int));
-            if (fail_flag) pcg_ok = false;
-            else if (host_pcg1[PCG_DONE] == 0.0) {
-                int rc = solve_reduced<DC>(h, host_pcg1, &pcg_iters, &pcg_ok, 1); if (rc) return rc;
-                SSFM_HIP_CHECK(ctx, hipMemset2DAsync(h->scal.p + SC_MODEL, SC_TOTAL * sizeof(double), 0, 4 * sizeof(double), SC_NSLOT, st));   // MODEL..CAND_COST of every replica
-                SSFM_HIP_CHECK(ctx, hipMemset2DAsync(h->scal.p + SC_STEP2_CAM, SC_TOTAL * sizeof(double), 0, 2 * sizeof(double), SC_NSLOT, st));   // and the camera norms
-                rc = enqueue_tail(true); if (rc) return rc;
-                rc = wait_iteration(); if (rc) return rc;
-                if (!poll) fold_host_scal();
-            }
+            back_substitute(res);
         }
+        const unsigned det_kt = det_tail_mask(with_cams, h->gram_fold);
+        if (h->det && !poll) det_decode(zone(iteration), false, det_kt);
+        if (ctx->collective) hipLaunchKernelGGL(k_scal_fold, dim3(1), dim3(SC_TOTAL * 64), 0, st, h->scal.p, (double*)nullptr, 0);
+        { const int rc = allreduce(h, h->scal.p + SC_MODEL, 4, ncclSum); if (rc) return rc; }   // MODEL, STEP2_PT, XN2_PT, CAND_COST
+        if (poll) {
+            spec_launched = may_speculate(with_cams);
+            if (spec_launched) { const LmGate g = gate(); publish(h, &g, h->lmdev.p, det_kt); }
+            else publish(h, nullptr, nullptr, det_kt);
+            return SSFM_OK;
+        }
+        SSFM_HIP_CHECK(ctx, hipMemcpyAsync(h->host_sp, h->scal.p, (SC_NSLOT * SC_TOTAL + PCG_TOTAL + 1) * sizeof(double), hipMemcpyDeviceToHost, st));   // scalars + solver flags
+        return SSFM_OK;
+    }
+    // what enqueue_tail accumulates, cleared in every replica before the tail is redone
+    int clear_tail_sums() {
+        SSFM_HIP_CHECK(ctx, hipMemset2DAsync(h->scal.p + SC_MODEL, SC_TOTAL * sizeof(double), 0, 4 * sizeof(double), SC_NSLOT, st));   // MODEL..CAND_COST of every replica
+        SSFM_HIP_CHECK(ctx, hipMemset2DAsync(h->scal.p + SC_STEP2_CAM, SC_TOTAL * sizeof(double), 0, 2 * sizeof(double), SC_NSLOT, st));   // and the camera norms
+        return SSFM_OK;
+    }
+    // the next zone's clear (unless k_finalize_gather did it) and the speculative launch behind the hand-over, while the host wakes up and decides
+    int speculate() {
+        const NextClear nc = next_clear();
+        if (!nc.in_finalize) SSFM_HIP_CHECK(ctx, hipMemsetAsync(nc.zone, 0, h->zone_len * sizeof(double), st));
+        if (!spec_launched) return SSFM_OK;
+        // x = this iteration's candidate, scalars into the next zone; [go, radius] from the device
+        if (fuse_lin) return launch_gram(c, zone(iteration + 1), (const double*)h->lmdev.p);
+        point_lin(c, nc.zone, (const double*)h->lmdev.p);
+        return SSFM_OK;
+    }
+    // the host goes another way than the device did: the next zone must be clean again
+    int undo_speculation() {
+        if (dev_go) SSFM_HIP_CHECK(ctx, hipMemsetAsync(next_clear().zone, 0, h->zone_len * sizeof(double), st));
+        if (dev_go && h->det) SSFM_HIP_CHECK(ctx, h->clear_det_lacc());   // the speculative point pass's sums
+        return SSFM_OK;
+    }
+    // the residual test of the direct solve failed (rare): PCG refinement, then the tail again
+    int refine_if_needed() {
+        if (O.preconditioner != 0) return SSFM_OK;
+        int fail_flag; std::memcpy(&fail_flag, &host_pcg1[PCG_TOTAL], sizeof(int));
+        if (fail_flag) { pcg_ok = false; return SSFM_OK; }
+        if (host_pcg1[PCG_DONE] != 0.0) return SSFM_OK;
+        int rc = solve_reduced<DC>(h, host_pcg1, &pcg_iters, &pcg_ok, 1); if (rc) return rc;
+        rc = clear_tail_sums(); if (rc) return rc;
+        rc = enqueue_tail(true); if (rc) return rc;
+        return wait_iteration();
+    }
+    void account() {
         h->pcg_prev_iters = pcg_iters; S->pcg_iterations_total += pcg_iters;
         if (phases) { float ms;
           if (hipEventElapsedTime(&ms, h->phase_ev[0], h->phase_ev[1]) == hipSuccess) ms_lin += ms;
@@ -446,31 +473,35 @@ static int lm_loop(ssfm_ba_handle* h, ssfm_ba_summary* S) {
           if (hipEventElapsedTime(&ms, h->phase_ev[3], h->phase_ev[4]) == hipSuccess) ms_upd += ms; }
         if (h->profile) h->resolve_spans();
         S->num_linearizations++;
-        // ================= host decisions (Ceres TrustRegionMinimizer, restated) =================
+    }
+
+    // ================= host decisions (Ceres TrustRegionMinimizer, restated; oracle/lm.hpp is the same text on the CPU) =================
+    // Host scalars only.  After LM_REJECTED / LM_INVALID the caller undoes the speculation.
+    LmStep decide() {
         x_cost = host_scal[SC_COST];
         double gmax; { unsigned long long bits; std::memcpy(&bits, &host_scal[SC_GMAX], 8); std::memcpy(&gmax, &bits, 8); }
         if (iteration == 1) { S->initial_cost = x_cost; minimum_cost = x_cost; }
-        if (!std::isfinite(x_cost)) { S->termination = SSFM_FAILURE; break; }
-        if (last_successful && gmax <= O.gradient_tolerance) { S->termination = SSFM_CONVERGENCE; iteration--; break; }
+        if (!std::isfinite(x_cost)) { S->termination = SSFM_FAILURE; return LM_TERMINATED; }
+        if (last_successful && gmax <= O.gradient_tolerance) { S->termination = SSFM_CONVERGENCE; iteration--; return LM_TERMINATED; }
         const double model_cost_change = -host_scal[SC_MODEL];
         const bool valid = pcg_ok && std::isfinite(model_cost_change) && model_cost_change > 0.0;
         if (!valid) {
-            if (++num_invalid >= O.max_num_consecutive_invalid_steps) { S->termination = SSFM_FAILURE; break; }
+            if (++num_invalid >= O.max_num_consecutive_invalid_steps) { S->termination = SSFM_FAILURE; return LM_TERMINATED; }
             radius /= decrease_factor; decrease_factor *= 2.0; last_successful = false; S->num_unsuccessful_steps++;
-            { int rc = undo_speculation(); if (rc) return rc; }
             if (O.verbose) std::printf("[ssfm ba] iter %4d invalid step (pcg %d its, model %.3e), radius %.3e\n", iteration, pcg_iters, model_cost_change, radius);
-            continue;
+            return LM_INVALID;
         }
         num_invalid = 0;
         double cand_cost = host_scal[SC_CAND_COST];
         if (!std::isfinite(cand_cost)) cand_cost = std::numeric_limits<double>::max();
         const double step_norm = std::sqrt(host_scal[SC_STEP2_PT] + host_scal[SC_STEP2_CAM]);
-        if (step_norm <= O.parameter_tolerance * (x_norm + O.parameter_tolerance)) { S->termination = SSFM_CONVERGENCE; break; }
+        if (step_norm <= O.parameter_tolerance * (x_norm + O.parameter_tolerance)) { S->termination = SSFM_CONVERGENCE; return LM_TERMINATED; }
         const double cost_change = x_cost - cand_cost;
-        if (std::fabs(cost_change) <= O.function_tolerance * x_cost) { S->termination = SSFM_CONVERGENCE; break; }
+        if (std::fabs(cost_change) <= O.function_tolerance * x_cost) { S->termination = SSFM_CONVERGENCE; return LM_TERMINATED; }
         const double rel = (cand_cost >= std::numeric_limits<double>::max()) ? std::numeric_limits<double>::lowest() : cost_change / model_cost_change;
-        if (rel > O.min_relative_decrease) {
-            std::swap(cam_x, cam_c); std::swap(pts_x, pts_c); std::swap(rot_x, rot_c); std::swap(fx, fc);
+        const bool accepted = rel > O.min_relative_decrease;
+        if (accepted) {
+            std::swap(x, c);
             x_norm = std::sqrt(host_scal[SC_XN2_PT] + host_scal[SC_XN2_CAM]);
             if (dev_go) { radius = dev_radius; lin_done = true; }     // the linearisation at the new x is already running with that radius
             else {
@@ -481,25 +512,91 @@ static int lm_loop(ssfm_ba_handle* h, ssfm_ba_summary* S) {
             x_cost = cand_cost; if (x_cost < minimum_cost) minimum_cost = x_cost;
         } else {
             radius /= decrease_factor; decrease_factor *= 2.0; last_successful = false; S->num_unsuccessful_steps++;
-            { int rc = undo_speculation(); if (rc) return rc; }
         }
         if (O.verbose)
             std::printf("[ssfm ba] iter %4d cost %.12e change %.3e |g|inf %.3e |step| %.3e rho %.3e radius %.3e pcg %d %s\n", iteration,
                         x_cost, cost_change, gmax, step_norm, rel, radius, pcg_iters, last_successful ? "" : "(rejected)");
+        return accepted ? LM_ACCEPTED : LM_REJECTED;
     }
-    // make the x buffers of the handle hold the final state
-    if (cam_x != h->cam_x.p || fx != h->focal3.p) {
-        const int nc = cam_x != h->cam_x.p ? Nc * 6 : 0, np = cam_x != h->cam_x.p ? nP * 3 : 0;
-        hipLaunchKernelGGL(k_copy_state, dim3((nc + np + 255) / 256 + 1), dim3(256), 0, st, h->cam_x.p, cam_x, nc, h->pts_x.p, pts_x, np,
-                           fx != h->focal3.p ? h->focal3.p : (double*)nullptr, fx);
+
+    // make the x buffers of the handle hold the final state; the summary
+    int finish() {
+        if (x.cam != h->cam_x.p || x.focal != h->focal3.p) {
+            const int nc = x.cam != h->cam_x.p ? Nc * 6 : 0, np = x.cam != h->cam_x.p ? nP * 3 : 0;
+            hipLaunchKernelGGL(k_copy_state, dim3((nc + np + 255) / 256 + 1), dim3(256), 0, st, h->cam_x.p, x.cam, nc, h->pts_x.p, x.pts, np,
+                               x.focal != h->focal3.p ? h->focal3.p : (double*)nullptr, x.focal);
+        }
+        SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+#ifdef SSFM_LAB
+        probe_Y.free(); probe_S.free();
+#endif
+        S->iterations = iteration;
+        S->final_cost = (minimum_cost == std::numeric_limits<double>::max()) ? x_cost : minimum_cost;
+        S->t_kernel_linearize_ms = ms_lin; S->t_kernel_schur_ms = ms_schur; S->t_kernel_pcg_ms = ms_pcg; S->t_kernel_update_ms = ms_upd;
+        return SSFM_OK;
     }
-    SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    probe_Y.free(); probe_S.free();
-    S->iterations = iteration;
-    S->final_cost = (minimum_cost == std::numeric_limits<double>::max()) ? x_cost : minimum_cost;
-    S->t_kernel_linearize_ms = ms_lin; S->t_kernel_schur_ms = ms_schur; S->t_kernel_pcg_ms = ms_pcg; S->t_kernel_update_ms = ms_upd;
-    return SSFM_OK;
-}
+
+    int run() {
+        int rc = startup(); if (rc) return rc;
+        while (true) {
+            if (iteration >= O.max_num_iterations) { S->termination = SSFM_NO_CONVERGENCE; break; }
+            if (radius <= O.min_trust_region_radius) { S->termination = SSFM_CONVERGENCE; break; }
+            iteration++;
+            rc = assemble(); if (rc) return rc;
+            rc = solve(); if (rc) return rc;
+            rc = enqueue_tail(!fused_cams); if (rc) return rc;
+            rc = record_phase(4); if (rc) return rc;
+            rc = speculate(); if (rc) return rc;
+            rc = wait_iteration(); if (rc) return rc;
+            dev_go = spec_launched && h->host_pub[SC_TOTAL + PCG_TOTAL + 2] == 1.0;
+            dev_radius = spec_launched ? h->host_pub[SC_TOTAL + PCG_TOTAL + 3] : 0.0;
+            SSFM_HIP_CHECK(ctx, hipGetLastError());                      // a launch that was refused (bad configuration) must not pass silently
+            rc = refine_if_needed(); if (rc) return rc;
+            account();
+            const LmStep step = decide();
+            if (step == LM_TERMINATED) break;
+            if (step != LM_ACCEPTED) { rc = undo_speculation(); if (rc) return rc; }
+        }
+        return finish();
+    }
+
+#ifdef SSFM_LAB
+    // ---- whole-path experiments, lab build only ----
+    // SSFM_PAIRS_Y_PROBE=1: the half-product variant of the pair pass runs next to the real kernel, on scratch data, for rocprofv3 (ba_kernels.h: k_pairs_y_probe)
+    static bool y_probe() { return SSFM_LAB_KNOB("SSFM_PAIRS_Y_PROBE", 0) != 0; }
+    int lab_y_probe_alloc() {
+        if (!y_probe()) return SSFM_OK;
+        SSFM_HIP_CHECK(ctx, probe_Y.alloc((size_t)F.M * DC * 3)); SSFM_HIP_CHECK(ctx, probe_S.alloc(h->zone_nnz));
+        SSFM_HIP_CHECK(ctx, hipMemsetAsync(probe_Y.p, 0x3c, (size_t)F.M * DC * 3 * sizeof(double), st)); SSFM_HIP_CHECK(ctx, hipMemsetAsync(probe_S.p, 0, h->zone_nnz * sizeof(double), st));
+        return SSFM_OK;
+    }
+    void lab_y_probe_launch() {
+        if (!y_probe() || F.chunk_cam.empty()) return;
+        const int ntasks = (int)F.chunk_cam.size();
+        hipLaunchKernelGGL(k_pairs_y_probe<DC>, dim3((ntasks + 3) / 4), dim3(256), 0, st, h->row_ptr.p, h->col_idx.p, h->chunk_cam.p, h->chunk_b0.p, h->chunk_b1.p, ntasks,
+                           h->batch_slot.p, h->pair_j.p, h->pair_j2.p, h->scale_cam.p, probe_Y.p, probe_S.p);
+    }
+    // SSFM_GRAM_STAMPS=1, timing study: per-task phase stamps of the first Gram launch of the process
+    static bool& gram_stamps_done() { static bool done = SSFM_LAB_KNOB("SSFM_GRAM_STAMPS", 0) == 0; return done; }
+    long long* lab_gram_stamps_begin(int ng) {
+        long long* gram_dbg = nullptr;
+        if (!gram_stamps_done()) (void)hipMalloc((void**)&gram_dbg, (size_t)4 * ng * sizeof(long long));
+        return gram_dbg;
+    }
+    void lab_gram_stamps_print(long long* gram_dbg, int ng) {      // print the phase times of this launch (100 MHz clock) and stop stamping
+        std::vector<long long> st2((size_t)4 * ng); (void)hipStreamSynchronize(h->ctx->stream); (void)hipMemcpy(st2.data(), gram_dbg, st2.size() * sizeof(long long), hipMemcpyDeviceToHost);
+        long long tmin = st2[0], tmax = 0; double a = 0, b = 0, c2 = 0;
+        for (int t = 0; t < ng; t++) { tmin = std::min(tmin, st2[4 * t]); tmax = std::max(tmax, st2[4 * t + 3]); a += st2[4 * t + 1] - st2[4 * t]; b += st2[4 * t + 2] - st2[4 * t + 1]; c2 += st2[4 * t + 3] - st2[4 * t + 2]; }
+        std::fprintf(stderr, "[gram] %d tasks, kernel span %.1f us; mean per task: start + first linearisation %.2f us, tiles + other sub-chunks %.2f us, emission %.2f us\n", ng, (tmax - tmin) * 0.01,
+                     a / ng * 0.01, b / ng * 0.01, c2 / ng * 0.01);
+        { double s_mean = 0, s_max = 0, e_mean = 0, a_max = 0, b_max = 0, c_max = 0;
+          for (int t = 0; t < ng; t++) { const double so = (st2[4 * t] - tmin) * 0.01; s_mean += so; s_max = std::max(s_max, so); e_mean += (st2[4 * t + 3] - tmin) * 0.01;
+                                         a_max = std::max(a_max, (st2[4 * t + 1] - st2[4 * t]) * 0.01); b_max = std::max(b_max, (st2[4 * t + 2] - st2[4 * t + 1]) * 0.01); c_max = std::max(c_max, (st2[4 * t + 3] - st2[4 * t + 2]) * 0.01); }
+          std::fprintf(stderr, "[gram] task start after the first: mean %.2f max %.2f us; task end mean %.2f us; longest phases %.2f | %.2f | %.2f us\n", s_mean / ng, s_max, e_mean / ng, a_max, b_max, c_max); }
+        (void)hipFree(gram_dbg); gram_stamps_done() = true;
+    }
+#endif
+};
 
 }  // namespace ssfm
 
@@ -756,9 +853,9 @@ static int ba_create_impl(ssfm_ctx* ctx, const ssfm_ba_problem* p, const ssfm_ba
     h->set_zone(0);
     if (h->det) {
         h->det_nacc = h->zone_nnz + 4 * n + 1;                      // [S | rhs (+ focal row) | diag U | S_fc | Jc^T r]: contiguous in the zone from S_val on
-        AL(det_limb, 2 * h->det_nacc + 2); AL(det_lacc, (size_t)SC_NSLOT * SC_TOTAL * LA_STRIDE); AL(det_dfpart, (size_t)std::max(1, (nP + 255) / 256));
+        AL(det_limb, 2 * h->det_nacc + 2); AL(det_lacc, h->det_lacc_words); AL(det_dfpart, (size_t)std::max(1, (nP + 255) / 256));
         SSFM_HIP_CHECK(ctx, hipMemsetAsync(h->det_limb.p, 0, (2 * h->det_nacc + 2) * sizeof(long long), st));
-        SSFM_HIP_CHECK(ctx, hipMemsetAsync(h->det_lacc.p, 0, (size_t)SC_NSLOT * SC_TOTAL * LA_STRIDE * sizeof(long long), st));
+        SSFM_HIP_CHECK(ctx, h->clear_det_lacc());
     }
     AL(Minv, (size_t)Nc * DC * DC); AL(Sff, 1);
     AL(px, n + 1); AL(pr, n + 1); AL(pz, n + 1); AL(pp, n + 1); AL(pq, n + 1); AL(pqpart, (size_t)Nc);
@@ -858,7 +955,7 @@ extern "C" int ssfm_ba_run(ssfm_ba_handle* h, ssfm_ba_summary* s) {
     SSFM_HIP_CHECK(h->ctx, hipSetDevice(h->ctx->device));
     std::memset(h->k_launches, 0, sizeof(h->k_launches)); std::memset(h->k_ms, 0, sizeof(h->k_ms));
     const double t0 = wall_s();
-    int rc = (F.DC == 3) ? lm_loop<3>(h, s) : lm_loop<6>(h, s);
+    int rc = (F.DC == 3) ? LmRun<3>(h, s).run() : LmRun<6>(h, s).run();
     s->t_solve_s = wall_s() - t0; s->reduced_blocks = nblk; s->band_half_width = F.band; s->band_segments = nsegs; s->band_separators = nseps;
     return rc;
 }
