@@ -294,6 +294,40 @@ int ssfm_ransac_batch_indexed_sharded(ssfm_ctx* ctx, int32_t num_frames, const i
 /* Measurement aid (the RANSAC leg is priced in FP64 flop/s of Sampson scoring, not GB/s): device time of the kernels of this context's last
  * ssfm_ransac_batch* call, summed over its slabs (hipEvent brackets on the solver stream; uploads and read-backs are outside).  No reference counterpart. */
 int ssfm_ransac_last_kernel_ms(ssfm_ctx* ctx, double* ms);
+/* ---- brute-force descriptor matching: match() / match_exhaustive() (examples/spherical_sfm_tools.cpp:235-251, :575-600) ---------------
+ * Per pair, train = the descriptors of frame pair_frame0[p] (n0 x dim floats), query = those of pair_frame1[p] (n1 x dim).  For every query i:
+ * its nearest train j1 and second nearest j2 by L2 distance (cv::BFMatcher::knnMatch(query, train, 2)), dist = sqrtf(sum (q - t)^2) as a float;
+ * if (double)dist1 < ratio * (double)dist2 then m01[j1] = i.  m01 is a std::map, so a later query overwrites an earlier one: the list of a pair is
+ * (j, i) in ascending j, each j once, i the LARGEST passing query whose nearest train is j -- what ImageMatch::matches holds and what
+ * ssfm_ransac_batch_indexed takes as match_idx0 / match_idx1.
+ * Device: distances as a tiled T . Q^T on the f32-input matrix instruction (exact f32), ranked by |t|^2 - 2 q.t with a running best / second best
+ * per query (the n1 x n0 matrix is never stored); the two finalists of a query are then re-evaluated as sum (q - t)^2 in f32, square-rooted
+ * (correctly rounded) and compared as above; an atomic max per train slot and a scan produce the lists.  Bit-identical from run to run.
+ * EXACT for SIFT descriptors (floats holding integers 0..255): every partial sum is an integer < 2^24, so every summation order and the product form
+ * give the same f32 and the lists equal the reference's.  For general floats the finalists may differ from OpenCV's where two candidates are within
+ * f32 rounding of each other (parity unpinned: OpenCV is not part of this build).
+ * Defined here, undefined in the reference: a pair whose train frame has fewer than 2 features yields no matches (the reference indexes past
+ * matches[i]); equal distances rank the lower train index first (this only shows for ratio >= 1: with ratio < 1 a tie dist1 == dist2 never passes
+ * and only the VALUE of dist2 enters the test). */
+typedef struct {
+    double ratio;       /* 0.75 (spherical_sfm_tools.h:70) */
+    int32_t dim;        /* 128; a multiple of 4, 4..128 */
+    int32_t reserved;
+} ssfm_match_options;
+void ssfm_match_default_options(ssfm_match_options* o);
+/* Frame f owns descriptors [feat_ptr[f], feat_ptr[f+1]) of descs ([feat_ptr[num_frames] * dim] floats, uploaded once per call).  Any number of pairs:
+ * they are processed in slabs that bound the slot buffer (environment SSFM_MATCH_SLAB_PAIRS, read at every call, forces the slab length).
+ * match_ptr [num_pairs + 1] is always written; match_idx0 / match_idx1 [capacity] may both be NULL (counts only).  If the total exceeds capacity the
+ * call returns SSFM_ERR_INVALID with the needed total in match_ptr[num_pairs] (the lists written so far are those of whole slabs that fitted).
+ * Arguments are checked before any launch (frame ids, dim, ratio > 0, ascending feat_ptr). */
+int ssfm_match_pairs(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, const float* descs, int32_t num_pairs,
+                     const int32_t* pair_frame0, const int32_t* pair_frame1, const ssfm_match_options* o, int64_t capacity,
+                     int32_t* match_ptr, int32_t* match_idx0, int32_t* match_idx1);
+/* Parity probe of ONE pair: per query i the finalists nn[2 i] = {j1, j2} (-1: the train set has no such row) and their float distances
+ * dist[2 i] = {dist1, dist2} (+inf where the index is -1).  nn [n1 * 2], dist [n1 * 2]. */
+int ssfm_match_knn_probe(ssfm_ctx* ctx, int32_t n0, const float* train, int32_t n1, const float* query, int32_t dim, int32_t* nn, float* dist);
+/* Device time of the kernels of this context's last ssfm_match_pairs call, summed over its slabs (like ssfm_ransac_last_kernel_ms). */
+int ssfm_match_last_kernel_ms(ssfm_ctx* ctx, double* ms);
 /* ---- the reference's estimator interface for ONE pair (rays resident on the device) ------------------------------------------------
  * One entry point per virtual of sphericalsfm::Estimator<Eigen::Matrix3d> / EssentialEstimator (include/sphericalsfm/estimator.h:7-29) as
  * SphericalEstimator implements them (include/sphericalsfm/spherical_estimator.h:8-35, src/spherical_estimator.cpp:67-164): what a host-side

@@ -71,6 +71,13 @@ class RansacOptionsC(C.Structure):
 RANSAC_FIXED_BUDGET, RANSAC_REFERENCE_TRACE = 0, 1
 
 
+class MatchOptionsC(C.Structure):
+    _fields_ = [("ratio", C.c_double), ("dim", C.c_int32), ("reserved", C.c_int32)]
+
+
+c_float_p = C.POINTER(C.c_float)
+
+
 # every symbol include/ssfm.h declares (tests check that the library exports all of them)
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_uint64, C.c_int32)
 
@@ -84,6 +91,7 @@ DECLARED_SYMBOLS = [
     "ssfm_minimal_solver_probe", "ssfm_sampson_probe",
     "ssfm_estimator_create", "ssfm_estimator_destroy", "ssfm_estimator_minimal_solver", "ssfm_estimator_non_minimal_solver",
     "ssfm_estimator_evaluate_model", "ssfm_estimator_least_squares", "ssfm_estimator_decompose",
+    "ssfm_match_default_options", "ssfm_match_pairs", "ssfm_match_knn_probe", "ssfm_match_last_kernel_ms",
 ]
 
 
@@ -177,6 +185,11 @@ def lib():
     L.ssfm_focal_search.argtypes = [vp, C.c_int32, C.c_int32, c_i32_p, c_i32_p, c_double_p, C.c_int32, C.c_double, C.c_int32, c_double_p, c_double_p,
                                     c_i32_p, c_double_p, c_double_p]
     L.ssfm_focal_search.restype = C.c_int
+    L.ssfm_match_default_options.argtypes = [C.POINTER(MatchOptionsC)]; L.ssfm_match_default_options.restype = None
+    L.ssfm_match_pairs.argtypes = [vp, C.c_int32, c_i32_p, c_float_p, C.c_int32, c_i32_p, c_i32_p, C.POINTER(MatchOptionsC), C.c_int64, c_i32_p, c_i32_p, c_i32_p]
+    L.ssfm_match_pairs.restype = C.c_int
+    L.ssfm_match_knn_probe.argtypes = [vp, C.c_int32, c_float_p, C.c_int32, c_float_p, C.c_int32, c_i32_p, c_float_p]; L.ssfm_match_knn_probe.restype = C.c_int
+    L.ssfm_match_last_kernel_ms.argtypes = [vp, c_double_p]; L.ssfm_match_last_kernel_ms.restype = C.c_int
     _LIB = L
     return L
 

@@ -2,8 +2,8 @@
 // reference intends past its debugging exit(0) at :81): read keyframes.txt / features.dat / matches.dat, sequential rotation
 // initialisation, rotation averaging, build_sfm, spherical BA -> Retriangulate -> BA, general BA -> Normalize -> Retriangulate -> BA
 // -> Normalize, then poses.txt, points.obj, cameras.obj and the COLMAP text model.  Everything numerical runs in libssfm_hip.so.
-// Feature detection / matching / pairwise RANSAC over images (the OpenCV front end) is outside this build; ssfm_ransac_batch is
-// the GPU replacement of the RANSAC step for callers that have the matches.
+// Feature detection over images (the OpenCV front end) is outside this build.  The library has the two steps after it -- ssfm_match_pairs
+// (match_exhaustive) and ssfm_ransac_batch (estimate_pairwise) -- but this driver does not call the matcher yet: it starts from a matches.dat.
 //   run_spherical_sfm -intrinsics <file: focal cx cy> -output <dir with the feature tracks> [-inward] [-width W -height H]
 #include <cstdio>
 #include <cstring>

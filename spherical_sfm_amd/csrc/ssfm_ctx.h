@@ -27,6 +27,7 @@ struct ssfm_ctx {
     // context (one stream, solves run one after the other): a hipHostMalloc per handle cost 0.2 ms of a 3 ms solve
     double* host_pub = nullptr; unsigned long long pub_seq = 0;
     double ransac_kernel_ms = 0.0;      // device time of the kernels of the last ssfm_ransac_batch* call (hipEvent brackets per slab), ssfm_ransac_last_kernel_ms
+    double match_kernel_ms = 0.0;       // the same for the last ssfm_match_pairs call, ssfm_match_last_kernel_ms
 };
 
 namespace ssfm {
