@@ -328,6 +328,32 @@ int ssfm_match_pairs(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr,
 int ssfm_match_knn_probe(ssfm_ctx* ctx, int32_t n0, const float* train, int32_t n1, const float* query, int32_t dim, int32_t* nn, float* dist);
 /* Device time of the kernels of this context's last ssfm_match_pairs call, summed over its slabs (like ssfm_ransac_last_kernel_ms). */
 int ssfm_match_last_kernel_ms(ssfm_ctx* ctx, double* ms);
+
+/* ---- the pairwise front end in one call: match_exhaustive + estimate_pairwise (examples/spherical_sfm_tools.cpp:575-600, :309-420) -------------
+ * For the given frame pairs, from the per-frame feature tables (descs: dim floats per feature; feat_rays: Kinv (x, y, 1), 3 doubles per feature; both
+ * indexed by feat_ptr like ssfm_match_pairs / ssfm_ransac_batch_indexed).  DEFINED by composition -- the outputs are, bit for bit, those of
+ *   1. ssfm_match_pairs on all pairs;
+ *   2. the candidates: pairs with count >= min_num_inliers and count > 0 (:353), in pair order;
+ *   3. ssfm_ransac_batch_indexed on exactly that candidate list (candidate k gets the random stream the indexed call gives its pair k);
+ *   4. the candidates with num_inliers > min_num_inliers (:410) and a non-empty inlier list; of these the INLIER matches only, ascending train index.
+ * The same kernels run with the same launch parameters; the match lists stay on the device between 1 and 3 and the inlier mask never leaves it: per pair
+ * only its match count (4 bytes) and, for candidates, num_inliers + stats come back, and for accepted pairs R, the count and the inlier lists.
+ * Outputs (capacity protocol): accepted_pair [pair_capacity] indices into the pair list, ascending; R [9 * pair_capacity] column-major;
+ * num_inliers [pair_capacity]; inl_ptr [pair_capacity + 1]; inl_idx0 / inl_idx1 [inlier_capacity] (features of frame0 / frame1).  All are required.
+ * needed[0] = accepted pairs, needed[1] = inlier matches, always written; if either exceeds its capacity the call returns SSFM_ERR_INVALID (no partial
+ * lists are promised) and is to be repeated with those sizes.  Optional per input pair: match_count [num_pairs], num_inliers_all [num_pairs] (-1 where
+ * the pair was no candidate), stats [2 * num_pairs] (iterations, LO runs; 0 where no candidate).  num_pairs = 0 and num_frames = 0 are fine.
+ * The argument checks run before any launch.  Single-GPU: a context with a communicator is refused (use ssfm_match_pairs +
+ * ssfm_ransac_batch_indexed_sharded there). */
+int ssfm_pairwise_from_features(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, const float* descs, const double* feat_rays,
+                                int32_t num_pairs, const int32_t* pair_frame0, const int32_t* pair_frame1, const ssfm_match_options* match_opt,
+                                const ssfm_ransac_options* ransac_opt, double squared_inlier_threshold, int64_t pair_capacity, int64_t inlier_capacity,
+                                int64_t* needed, int32_t* accepted_pair, double* R, int32_t* num_inliers, int32_t* inl_ptr, int32_t* inl_idx0,
+                                int32_t* inl_idx1, int32_t* match_count, int32_t* num_inliers_all, uint32_t* stats);
+/* Device time of the kernels of this context's last ssfm_pairwise_from_features call: the brackets of ssfm_match_last_kernel_ms and
+ * ssfm_ransac_last_kernel_ms, the latter with the hand-over kernels inside.  NOT included: the device-to-device copies that append every match slab's lists
+ * to the call's list (8 bytes per match, once; copied again when the list has to grow), which run between the two brackets. */
+int ssfm_pairwise_front_last_kernel_ms(ssfm_ctx* ctx, double* ms);
 /* ---- the reference's estimator interface for ONE pair (rays resident on the device) ------------------------------------------------
  * One entry point per virtual of sphericalsfm::Estimator<Eigen::Matrix3d> / EssentialEstimator (include/sphericalsfm/estimator.h:7-29) as
  * SphericalEstimator implements them (include/sphericalsfm/spherical_estimator.h:8-35, src/spherical_estimator.cpp:67-164): what a host-side

@@ -27,6 +27,7 @@
 #include <limits>
 #include <vector>
 #include "ssfm_ctx.h"
+#include "pairwise_front.h"
 
 namespace ssfm {
 
@@ -193,21 +194,6 @@ k_match_dist(const MatchPair* __restrict__ pairs, const float* __restrict__ desc
     }
 }
 
-// exclusive prefix sum of one int per thread over a 256-thread workgroup; *total = the sum
-__device__ __forceinline__ int block_exclusive_scan(int v, int* total) {
-    __shared__ int wsum[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o); if (lane >= o) inc += u; }
-    __syncthreads();                                               // (wsum of the previous call has been read)
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = 0, all = 0;
-    for (int w = 0; w < 4; w++) { if (w < wave) base += wsum[w]; all += wsum[w]; }
-    *total = all;
-    return base + inc - v;
-}
-
 static __global__ void __launch_bounds__(256) k_match_count(const MatchPair* __restrict__ pairs, const int* __restrict__ slots, int slot_stride, int* __restrict__ counts) {
     const int p = blockIdx.x, n0 = pairs[p].n0;
     int c = 0;
@@ -261,44 +247,31 @@ static int upload_descs(ssfm_ctx* ctx, MatchDevice& D, size_t total, int dim, co
 
 static bool dim_ok(int dim) { return dim >= 4 && dim <= MK && dim % 4 == 0; }
 
-}  // namespace ssfm
-
-using namespace ssfm;
-
-extern "C" void ssfm_match_default_options(ssfm_match_options* o) {
-    if (!o) return;
-    o->ratio = 0.75; o->dim = 128; o->reserved = 0;
-}
-
-extern "C" int ssfm_match_last_kernel_ms(ssfm_ctx* ctx, double* ms) {
-    if (!ctx || !ms) return SSFM_ERR_INVALID;
-    *ms = ctx->match_kernel_ms;
+int match_check_args(ssfm_ctx* ctx, const char* who, int32_t num_frames, const int32_t* feat_ptr, const float* descs, int32_t num_pairs, const int32_t* pair_frame0,
+                     const int32_t* pair_frame1, const ssfm_match_options* opt, ssfm_match_options* O) {
+    const std::string w(who);
+    if (num_frames <= 0 || !feat_ptr || num_pairs < 0 || (num_pairs > 0 && (!pair_frame0 || !pair_frame1)))
+        return fail(ctx, SSFM_ERR_INVALID, w + ": bad arguments (num_frames > 0, feat_ptr and the pair lists are required)");
+    ssfm_match_default_options(O); if (opt) *O = *opt;
+    if (!dim_ok(O->dim)) return fail(ctx, SSFM_ERR_INVALID, w + ": dim must be a multiple of 4 in 4..128");
+    if (!(O->ratio > 0.0) || !std::isfinite(O->ratio)) return fail(ctx, SSFM_ERR_INVALID, w + ": ratio must be positive and finite");
+    if (feat_ptr[0] != 0) return fail(ctx, SSFM_ERR_INVALID, w + ": feat_ptr[0] must be 0");
+    for (int f = 0; f < num_frames; f++) if (feat_ptr[f + 1] < feat_ptr[f]) return fail(ctx, SSFM_ERR_INVALID, w + ": feat_ptr must ascend");
+    if (feat_ptr[num_frames] && !descs) return fail(ctx, SSFM_ERR_INVALID, w + ": descs is null");
+    for (int p = 0; p < num_pairs; p++) {
+        const int f0 = pair_frame0[p], f1 = pair_frame1[p];
+        if (f0 < 0 || f0 >= num_frames || f1 < 0 || f1 >= num_frames) return fail(ctx, SSFM_ERR_INVALID, w + ": frame index out of range");
+    }
     return SSFM_OK;
 }
 
-extern "C" int ssfm_match_pairs(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, const float* descs, int32_t num_pairs, const int32_t* pair_frame0,
-                                const int32_t* pair_frame1, const ssfm_match_options* opt, int64_t capacity, int32_t* match_ptr, int32_t* match_idx0,
-                                int32_t* match_idx1) {
-    if (!ctx) return SSFM_ERR_INVALID;
-    if (num_frames <= 0 || !feat_ptr || num_pairs < 0 || (num_pairs > 0 && (!pair_frame0 || !pair_frame1)) || !match_ptr || capacity < 0)
-        return fail(ctx, SSFM_ERR_INVALID, "ssfm_match_pairs: bad arguments (num_frames > 0, feat_ptr, the pair lists and match_ptr are required)");
-    if ((match_idx0 == nullptr) != (match_idx1 == nullptr)) return fail(ctx, SSFM_ERR_INVALID, "ssfm_match_pairs: match_idx0 and match_idx1 are given together or not at all");
-    ssfm_match_options O; ssfm_match_default_options(&O); if (opt) O = *opt;
-    if (!dim_ok(O.dim)) return fail(ctx, SSFM_ERR_INVALID, "ssfm_match_pairs: dim must be a multiple of 4 in 4..128");
-    if (!(O.ratio > 0.0) || !std::isfinite(O.ratio)) return fail(ctx, SSFM_ERR_INVALID, "ssfm_match_pairs: ratio must be positive and finite");
-    if (feat_ptr[0] != 0) return fail(ctx, SSFM_ERR_INVALID, "ssfm_match_pairs: feat_ptr[0] must be 0");
-    for (int f = 0; f < num_frames; f++) if (feat_ptr[f + 1] < feat_ptr[f]) return fail(ctx, SSFM_ERR_INVALID, "ssfm_match_pairs: feat_ptr must ascend");
+int match_slabs(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, const float* descs, int32_t num_pairs, const int32_t* pair_frame0,
+                const int32_t* pair_frame1, const ssfm_match_options& O, const MatchSlabSink& sink) {
     const size_t total = (size_t)feat_ptr[num_frames];
-    if (total && !descs) return fail(ctx, SSFM_ERR_INVALID, "ssfm_match_pairs: descs is null");
     int max_n0 = 1;
-    for (int p = 0; p < num_pairs; p++) {
-        const int f0 = pair_frame0[p], f1 = pair_frame1[p];
-        if (f0 < 0 || f0 >= num_frames || f1 < 0 || f1 >= num_frames) return fail(ctx, SSFM_ERR_INVALID, "ssfm_match_pairs: frame index out of range");
-        max_n0 = std::max(max_n0, feat_ptr[f0 + 1] - feat_ptr[f0]);
-    }
+    for (int p = 0; p < num_pairs; p++) max_n0 = std::max(max_n0, feat_ptr[pair_frame0[p] + 1] - feat_ptr[pair_frame0[p]]);
     SSFM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     ctx->match_kernel_ms = 0.0;
-    match_ptr[0] = 0;
     if (num_pairs == 0) return SSFM_OK;
     // slabs: the slot buffer (pairs of the slab x max n0 x 4 B) stays within 64 MB; SSFM_MATCH_SLAB_PAIRS (read at every call) overrides the pair count
     int slab_pairs = (int)std::min<size_t>(32768, std::max<size_t>(1, ((size_t)16 << 20) / (size_t)max_n0));
@@ -307,7 +280,6 @@ extern "C" int ssfm_match_pairs(ssfm_ctx* ctx, int32_t num_frames, const int32_t
     hipStream_t st = ctx->stream;
     MatchDevice D;
     std::vector<MatchPair> hp((size_t)slab_pairs); std::vector<int> hptr((size_t)slab_pairs + 1);
-    int64_t running = 0; bool overflow = false;
     auto body = [&]() -> int {
         { const int r = upload_descs(ctx, D, total, O.dim, descs); if (r) return r; }
         const size_t nslot = (size_t)slab_pairs * max_n0;
@@ -336,24 +308,58 @@ extern "C" int ssfm_match_pairs(ssfm_ctx* ctx, int32_t num_frames, const int32_t
             SSFM_HIP_CHECK(ctx, hipMemcpyAsync(hptr.data(), D.ptr.p, ((size_t)np + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
             SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
             { float ms = 0.f; if (hipEventElapsedTime(&ms, D.e0, D.e1) == hipSuccess) ctx->match_kernel_ms += ms; else (void)hipGetLastError(); }
-            const int64_t slab_total = hptr[np];
-            if (running + slab_total > (int64_t)std::numeric_limits<int32_t>::max()) return fail(ctx, SSFM_ERR_INVALID, "ssfm_match_pairs: more than INT32_MAX matches in one call");
-            for (int i = 1; i <= np; i++) match_ptr[p0 + i] = (int32_t)(running + hptr[i]);
-            if (match_idx0) {
-                if (running + slab_total > capacity) overflow = true;      // keep counting: match_ptr[num_pairs] reports the capacity needed
-                else if (slab_total) {
-                    SSFM_HIP_CHECK(ctx, hipMemcpyAsync(match_idx0 + running, D.idx0.p, (size_t)slab_total * sizeof(int), hipMemcpyDeviceToHost, st));
-                    SSFM_HIP_CHECK(ctx, hipMemcpyAsync(match_idx1 + running, D.idx1.p, (size_t)slab_total * sizeof(int), hipMemcpyDeviceToHost, st));
-                    SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-                }
-            }
-            running += slab_total;
+            { const int r = sink(p0, np, hptr.data(), D.idx0.p, D.idx1.p); if (r) return r; }
         }
         return SSFM_OK;
     };
-    int rc = body();
+    const int rc = body();
     (void)hipStreamSynchronize(st);
     D.release();
+    return rc;
+}
+
+}  // namespace ssfm
+
+using namespace ssfm;
+
+extern "C" void ssfm_match_default_options(ssfm_match_options* o) {
+    if (!o) return;
+    o->ratio = 0.75; o->dim = 128; o->reserved = 0;
+}
+
+extern "C" int ssfm_match_last_kernel_ms(ssfm_ctx* ctx, double* ms) {
+    if (!ctx || !ms) return SSFM_ERR_INVALID;
+    *ms = ctx->match_kernel_ms;
+    return SSFM_OK;
+}
+
+extern "C" int ssfm_match_pairs(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, const float* descs, int32_t num_pairs, const int32_t* pair_frame0,
+                                const int32_t* pair_frame1, const ssfm_match_options* opt, int64_t capacity, int32_t* match_ptr, int32_t* match_idx0,
+                                int32_t* match_idx1) {
+    if (!ctx) return SSFM_ERR_INVALID;
+    if (num_frames <= 0 || !feat_ptr || num_pairs < 0 || (num_pairs > 0 && (!pair_frame0 || !pair_frame1)) || !match_ptr || capacity < 0)
+        return fail(ctx, SSFM_ERR_INVALID, "ssfm_match_pairs: bad arguments (num_frames > 0, feat_ptr, the pair lists and match_ptr are required)");
+    if ((match_idx0 == nullptr) != (match_idx1 == nullptr)) return fail(ctx, SSFM_ERR_INVALID, "ssfm_match_pairs: match_idx0 and match_idx1 are given together or not at all");
+    ssfm_match_options O;
+    { const int r = match_check_args(ctx, "ssfm_match_pairs", num_frames, feat_ptr, descs, num_pairs, pair_frame0, pair_frame1, opt, &O); if (r) return r; }
+    match_ptr[0] = 0;
+    hipStream_t st = ctx->stream;
+    int64_t running = 0; bool overflow = false;
+    int rc = match_slabs(ctx, num_frames, feat_ptr, descs, num_pairs, pair_frame0, pair_frame1, O, [&](int p0, int np, const int* hptr, const int* d_idx0, const int* d_idx1) -> int {
+        const int64_t slab_total = hptr[np];
+        if (running + slab_total > (int64_t)std::numeric_limits<int32_t>::max()) return fail(ctx, SSFM_ERR_INVALID, "ssfm_match_pairs: more than INT32_MAX matches in one call");
+        for (int i = 1; i <= np; i++) match_ptr[p0 + i] = (int32_t)(running + hptr[i]);
+        if (match_idx0) {
+            if (running + slab_total > capacity) overflow = true;      // keep counting: match_ptr[num_pairs] reports the capacity needed
+            else if (slab_total) {
+                SSFM_HIP_CHECK(ctx, hipMemcpyAsync(match_idx0 + running, d_idx0, (size_t)slab_total * sizeof(int), hipMemcpyDeviceToHost, st));
+                SSFM_HIP_CHECK(ctx, hipMemcpyAsync(match_idx1 + running, d_idx1, (size_t)slab_total * sizeof(int), hipMemcpyDeviceToHost, st));
+                SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+            }
+        }
+        running += slab_total;
+        return SSFM_OK;
+    });
     if (rc == SSFM_OK && overflow) rc = fail(ctx, SSFM_ERR_INVALID, "ssfm_match_pairs: capacity too small; match_ptr[num_pairs] holds the number of matches");
     return rc;
 }

@@ -20,6 +20,7 @@
 #include <thread>
 #include "ransac_device.h"
 #include "sampson_lsq.h"
+#include "pairwise_front.h"
 
 namespace ssfm {
 
@@ -220,7 +221,9 @@ bool lomsac_needs_global_lists(int max_n);
 // than one allocation should hold and far more than one copy should block on): slab k+1 is packed into the second pinned buffer and copied
 // on the context's copy stream while slab k computes; results come back per slab.  One slab = at most SLAB_RAYS rays / SLAB_PAIRS pairs.
 // indexed input (ssfm_ransac_batch_indexed): rays come from per-frame feature tables through per-pair match lists
-struct RansacIndexed { int32_t num_frames; const int32_t* feat_ptr; const double* feat_rays; const int32_t* frame0; const int32_t* frame1; const int32_t* idx0; const int32_t* idx1; };
+// dev != nullptr (ssfm_pairwise_from_features): the match lists are already on the device -- idx0 / idx1 / feat_rays are unused, the hooks stage, gather and collect
+struct RansacIndexed { int32_t num_frames; const int32_t* feat_ptr; const double* feat_rays; const int32_t* frame0; const int32_t* frame1; const int32_t* idx0; const int32_t* idx1;
+                       ssfm::RansacDeviceLists* dev = nullptr; };
 // one workgroup per pair: u[i] = rays[off0 + idx0[i]], v[i] = rays[off1 + idx1[i]]
 static __global__ void __launch_bounds__(256)
 k_gather_rays(const int* __restrict__ ptr, const int* __restrict__ off01, const int* __restrict__ idx0, const int* __restrict__ idx1, const double* __restrict__ rays,
@@ -274,7 +277,9 @@ static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pa
     auto body = [&]() -> int {
         if (trace) { std::vector<unsigned> seeded(624); mt_seed_host(O.seed, seeded.data()); SSFM_HIP_CHECK(ctx, upload(dmt, seeded, st)); }
         if (nslot > 1) { SSFM_HIP_CHECK(ctx, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking)); }
-        if (X) {                                              // the feature rays of every frame, once
+        RansacDeviceLists* const dev = X ? X->dev : nullptr;
+        if (dev) { const int r = dev->prepare(nslot, cap_pairs, cap_rays); if (r) return r; }
+        else if (X) {                                         // the feature rays of every frame, once
             const size_t nf = (size_t)X->feat_ptr[X->num_frames];
             SSFM_HIP_CHECK(ctx, frays.alloc(std::max<size_t>(1, 3 * nf)));
             if (nf) SSFM_HIP_CHECK(ctx, hipMemcpyAsync(frays.p, X->feat_rays, 3 * nf * sizeof(double), hipMemcpyHostToDevice, st));
@@ -289,12 +294,13 @@ static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pa
             SSFM_HIP_CHECK(ctx, s.S.alloc(cap_pairs)); SSFM_HIP_CHECK(ctx, s.R.alloc((size_t)9 * cap_pairs)); SSFM_HIP_CHECK(ctx, s.mask.alloc(cap_rays));
             SSFM_HIP_CHECK(ctx, s.stats.alloc((size_t)2 * cap_pairs));
             if (glists) SSFM_HIP_CHECK(ctx, s.lists.alloc((trace ? 2 : 1) * cap_rays));
-            if (X) { SSFM_HIP_CHECK(ctx, s.idx.alloc(2 * cap_rays)); SSFM_HIP_CHECK(ctx, s.off.alloc((size_t)2 * cap_pairs));
+            if (dev) {}                                       // (the hooks own the per-slot list buffers)
+            else if (X) { SSFM_HIP_CHECK(ctx, s.idx.alloc(2 * cap_rays)); SSFM_HIP_CHECK(ctx, s.off.alloc((size_t)2 * cap_pairs));
                      SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_idx, (2 * cap_rays + (size_t)2 * cap_pairs) * sizeof(int), hipHostMallocDefault)); }
             else SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_uv, 6 * cap_rays * sizeof(double), hipHostMallocDefault));
             SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_ptr, (size_t)(2 * cap_pairs + 1) * sizeof(int), hipHostMallocDefault));
             SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_res, (size_t)19 * cap_pairs * sizeof(double), hipHostMallocDefault));
-            SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_mask, cap_rays, hipHostMallocDefault));
+            if (!dev) SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_mask, cap_rays, hipHostMallocDefault));
             SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_nin, (size_t)cap_pairs * sizeof(int), hipHostMallocDefault));
             SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_stats, (size_t)2 * cap_pairs * sizeof(unsigned), hipHostMallocDefault));
         }
@@ -302,7 +308,8 @@ static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pa
             Slot& s = slot[k % nslot]; hipStream_t up = (nslot > 1) ? cs : st;
             const int p0 = slab[k], np = slab[k + 1] - p0, r0 = pair_ptr[p0]; const size_t nr = (size_t)(pair_ptr[slab[k + 1]] - r0);
             if (k >= nslot) SSFM_HIP_CHECK(ctx, hipEventSynchronize(compute_done[k % nslot]));      // the slot's previous slab has been read back
-            if (X) {                                          // match lists + the two feature offsets of every pair; the rays are gathered on the device
+            if (dev) { const int r = dev->stage(up, k % nslot, p0, np); if (r) return r; }
+            else if (X) {                                     // match lists + the two feature offsets of every pair; the rays are gathered on the device
                 // copied AND range-checked here, on the staging threads (a check of the whole list up front would be a second pass over 8 GB at configs[3])
                 int* ho = s.h_idx + 2 * cap_rays;
                 std::atomic<int> bad(0);
@@ -358,6 +365,7 @@ static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pa
             const int p0 = slab[k], np = slab[k + 1] - p0, r0 = pair_ptr[p0]; const size_t nr = (size_t)(pair_ptr[slab[k + 1]] - r0);
             SSFM_HIP_CHECK(ctx, hipEventSynchronize(compute_done[k % nslot]));
             { float ms = 0.0f; if (hipEventElapsedTime(&ms, kt0[k % nslot], kt1[k % nslot]) == hipSuccess) ctx->ransac_kernel_ms += ms; else (void)hipGetLastError(); }
+            if (dev) { const int r = dev->collect(cs ? cs : st, k % nslot, p0, np); if (r) return r; }
             for (int i = 0; i < np; i++) {
                 if (E_out) rm_to_cm(s.h_res + 9 * (size_t)i, E_out + 9 * (size_t)(p0 + i));
                 if (R_out) rm_to_cm(s.h_res + 9 * (size_t)cap_pairs + 9 * (size_t)i, R_out + 9 * (size_t)(p0 + i));
@@ -375,7 +383,8 @@ static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pa
             int slab_max_n = 0; for (int p = slab[k]; p < slab[k + 1]; p++) slab_max_n = std::max(slab_max_n, pair_ptr[p + 1] - pair_ptr[p]);
             SSFM_HIP_CHECK(ctx, hipStreamWaitEvent(st, up_done[k % nslot], 0));
             SSFM_HIP_CHECK(ctx, hipEventRecord(kt0[k % nslot], st));
-            if (X && np > 0) hipLaunchKernelGGL(k_gather_rays, dim3(np), dim3(256), 0, st, s.ptr.p, s.off.p, s.idx.p, s.idx.p + cap_rays, frays.p, s.u.p, s.v.p);
+            if (dev) { const int r = dev->gather(st, k % nslot, np, s.ptr.p, s.u.p, s.v.p); if (r) return r; }
+            else if (X && np > 0) hipLaunchKernelGGL(k_gather_rays, dim3(np), dim3(256), 0, st, s.ptr.p, s.off.p, s.idx.p, s.idx.p + cap_rays, frays.p, s.u.p, s.v.p);
             if (trace) {
                 const int r = lomsac_launch(ctx, st, np, slab_max_n, s.ptr.p, s.u.p, s.v.p, (int)nr, O, sq_thresh, dmt.p, glists ? s.lists.p : nullptr, s.E.p, s.S.p, s.R.p, s.mask.p, s.nin.p, s.stats.p);
                 if (r) return r;
@@ -392,11 +401,14 @@ static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pa
                                    s.lists.p, s.E.p, s.S.p, s.R.p, s.mask.p, s.nin.p);
                 SSFM_HIP_CHECK(ctx, hipMemsetAsync(s.stats.p, 0, (size_t)2 * np * sizeof(unsigned), st));
             }
+            if (dev) { const int r = dev->lists(st, k % nslot, np, s.ptr.p, s.mask.p, s.nin.p, s.R.p); if (r) return r; }      // inside the kernel bracket
             SSFM_HIP_CHECK(ctx, hipEventRecord(kt1[k % nslot], st));
-            SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_res, s.E.p, (size_t)9 * np * sizeof(double), hipMemcpyDeviceToHost, st));
-            SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_res + 9 * (size_t)cap_pairs, s.R.p, (size_t)9 * np * sizeof(double), hipMemcpyDeviceToHost, st));
-            SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_res + 18 * (size_t)cap_pairs, s.S.p, (size_t)np * sizeof(double), hipMemcpyDeviceToHost, st));
-            if (nr) SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_mask, s.mask.p, nr, hipMemcpyDeviceToHost, st));
+            if (!dev) {                                       // (the hooks bring back the accepted pairs' R and inlier lists; E, the scores and the mask stay on the device)
+                SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_res, s.E.p, (size_t)9 * np * sizeof(double), hipMemcpyDeviceToHost, st));
+                SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_res + 9 * (size_t)cap_pairs, s.R.p, (size_t)9 * np * sizeof(double), hipMemcpyDeviceToHost, st));
+                SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_res + 18 * (size_t)cap_pairs, s.S.p, (size_t)np * sizeof(double), hipMemcpyDeviceToHost, st));
+                if (nr) SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_mask, s.mask.p, nr, hipMemcpyDeviceToHost, st));
+            }
             SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_nin, s.nin.p, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, st));
             SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_stats, s.stats.p, (size_t)2 * np * sizeof(unsigned), hipMemcpyDeviceToHost, st));
             SSFM_HIP_CHECK(ctx, hipEventRecord(compute_done[k % nslot], st));
@@ -420,6 +432,14 @@ static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pa
     if (cs) (void)hipStreamDestroy(cs);
     return rc;
 }
+
+namespace ssfm {
+int ransac_on_device_lists(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, int32_t num_pairs, const int32_t* pair_frame0, const int32_t* pair_frame1,
+                           const int32_t* pair_ptr, double sq_thresh, const ssfm_ransac_options& O, RansacDeviceLists* hooks, int32_t* num_inliers, uint32_t* stats) {
+    const RansacIndexed X{num_frames, feat_ptr, nullptr, pair_frame0, pair_frame1, nullptr, nullptr, hooks};
+    return ransac_batch_impl(ctx, num_pairs, pair_ptr, nullptr, nullptr, sq_thresh, O, nullptr, nullptr, nullptr, nullptr, num_inliers, nullptr, stats, &X);
+}
+}  // namespace ssfm
 
 extern "C" int ssfm_ransac_last_kernel_ms(ssfm_ctx* ctx, double* ms) {
     if (!ctx || !ms) return SSFM_ERR_INVALID;

@@ -2,9 +2,10 @@
 // reference intends past its debugging exit(0) at :81): read keyframes.txt / features.dat / matches.dat, sequential rotation
 // initialisation, rotation averaging, build_sfm, spherical BA -> Retriangulate -> BA, general BA -> Normalize -> Retriangulate -> BA
 // -> Normalize, then poses.txt, points.obj, cameras.obj and the COLMAP text model.  Everything numerical runs in libssfm_hip.so.
-// Feature detection over images (the OpenCV front end) is outside this build.  The library has the two steps after it -- ssfm_match_pairs
-// (match_exhaustive) and ssfm_ransac_batch (estimate_pairwise) -- but this driver does not call the matcher yet: it starts from a matches.dat.
-//   run_spherical_sfm -intrinsics <file: focal cx cy> -output <dir with the feature tracks> [-inward] [-width W -height H]
+// Feature detection over images (the OpenCV front end) is outside this build.  With -match the driver starts from keyframes.txt + features.dat alone, as the
+// reference's driver does after detect_features (:49-55): match_exhaustive + estimate_pairwise in one device call (estimate_pairwise_from_features), then
+// find_largest_connected_component.  Without it, it starts from a matches.dat (-pairwise: that file holds raw matches, estimate_pairwise runs first).
+//   run_spherical_sfm -intrinsics <file: focal cx cy> -output <dir with the feature tracks> [-match | -pairwise] [-inward] [-width W -height H]
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -13,7 +14,7 @@
 using namespace sphericalsfm;
 
 int main(int argc, char** argv) {
-    std::string intrinsics_path, output; bool inward = false, pairwise = false; int width = 1920, height = 1080, mininliers = 100; double inlierthresh = 2.0;
+    std::string intrinsics_path, output; bool inward = false, pairwise = false, match_mode = false; int width = 1920, height = 1080, mininliers = 100; double inlierthresh = 2.0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "-intrinsics" && i + 1 < argc) intrinsics_path = argv[++i];
@@ -22,6 +23,7 @@ int main(int argc, char** argv) {
         else if (a == "-height" && i + 1 < argc) height = std::atoi(argv[++i]);
         else if (a == "-inward") inward = true;
         else if (a == "-pairwise") pairwise = true;                         // matches.dat holds raw matches: run estimate_pairwise (GPU RANSAC) first
+        else if (a == "-match") match_mode = true;                          // no matches.dat: features -> verified image matches on the device
         else if (a == "-inlierthresh" && i + 1 < argc) inlierthresh = std::atof(argv[++i]);
         else if (a == "-mininliers" && i + 1 < argc) mininliers = std::atoi(argv[++i]);
         else if (a == "-sequential") {}                                     // the only rotation initialisation available here
@@ -35,12 +37,22 @@ int main(int argc, char** argv) {
     Intrinsics intrinsics(focal, centerx, centery);
 
     std::vector<Keyframe> keyframes; std::vector<ImageMatch> image_matches;
-    if (!read_feature_tracks(output, keyframes, image_matches)) { std::cout << "error: no feature tracks in " << output << "\n"; return 1; }
-    if (image_matches.empty()) { std::cout << "error: no loop closures found\n"; return 1; }
+    if (match_mode) { if (!read_features(output, keyframes)) { std::cout << "error: no features in " << output << "\n"; return 1; } }
+    else {
+        if (!read_feature_tracks(output, keyframes, image_matches)) { std::cout << "error: no feature tracks in " << output << "\n"; return 1; }
+        if (image_matches.empty()) { std::cout << "error: no loop closures found\n"; return 1; }
+    }
 
     SfM sfm(intrinsics);
     int loop_closures = -1;
-    if (pairwise) {                                                          // run_spherical_sfm.cpp:56-63
+    if (match_mode) {                                                        // run_spherical_sfm.cpp:49-55
+        std::cout << "matching and detecting loop closures\n";
+        const size_t nframes = keyframes.size();
+        loop_closures = estimate_pairwise_from_features(sfm.GetContext(), intrinsics, keyframes, inlierthresh, mininliers, inward, image_matches);
+        if (loop_closures == 0) { std::cout << "error: no loop closures found\n"; return 1; }
+        find_largest_connected_component(keyframes, image_matches);
+        std::cout << "kept " << keyframes.size() << " of " << nframes << " keyframes, " << image_matches.size() << " image pairs, " << loop_closures << " loop closures\n";
+    } else if (pairwise) {                                                          // run_spherical_sfm.cpp:56-63
         std::cout << "detecting loop closures\n";
         std::vector<ImageMatch> all_image_matches; all_image_matches.swap(image_matches);
         loop_closures = estimate_pairwise(sfm.GetContext(), intrinsics, keyframes, all_image_matches, inlierthresh, mininliers, inward, image_matches);

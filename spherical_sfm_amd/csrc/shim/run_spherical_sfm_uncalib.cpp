@@ -3,14 +3,18 @@
 // graph + joint refinement (find_best_focal_length_random), build_sfm at the found focal, shared focal FREE in every bundle
 // adjustment: spherical BA -> Retriangulate -> BA, with -generalba: unfix translations -> BA -> Normalize -> Retriangulate -> BA ->
 // Normalize; poses.txt, OBJ files, COLMAP text model, calib.txt.  Everything numerical runs in libssfm_hip.so.
+// -match: no matches.dat -- match_exhaustive + estimate_pairwise at the guessed focal in one device call (estimate_pairwise_from_features), then
+// find_largest_connected_component (:96-122).
 //   run_spherical_sfm_uncalib -output <dir with keyframes.txt, features.dat, matches.dat> -width W -height H [-generalba] [-inward]
+//                             [-match [-inlierthresh T] [-mininliers N]]
 #include <cstdio>
+#include <cstdlib>
 #include <iostream>
 #include "tools.h"
 using namespace sphericalsfm;
 
 int main(int argc, char** argv) {
-    std::string output; bool inward = false, generalba = false; int width = 0, height = 0, num_trials = 1024; unsigned seed = 0;
+    std::string output; bool inward = false, generalba = false, match_mode = false; int width = 0, height = 0, num_trials = 1024, mininliers = 100; unsigned seed = 0; double inlierthresh = 2.0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "-output" && i + 1 < argc) output = argv[++i];
@@ -20,17 +24,27 @@ int main(int argc, char** argv) {
         else if (a == "-seed" && i + 1 < argc) seed = (unsigned)std::atoi(argv[++i]);
         else if (a == "-inward") inward = true;
         else if (a == "-generalba") generalba = true;
+        else if (a == "-match") match_mode = true;
+        else if (a == "-inlierthresh" && i + 1 < argc) inlierthresh = std::atof(argv[++i]);
+        else if (a == "-mininliers" && i + 1 < argc) mininliers = std::atoi(argv[++i]);
         else if (a == "-sequential") {}
         else { std::cout << "unknown argument " << a << "\n"; return 2; }
     }
     if (output.empty() || width <= 0 || height <= 0) { std::cout << "usage: run_spherical_sfm_uncalib -output <dir> -width W -height H [-generalba] [-inward]\n"; return 2; }
     std::vector<Keyframe> keyframes; std::vector<ImageMatch> image_matches;
-    if (!read_feature_tracks(output, keyframes, image_matches) || image_matches.empty()) { std::cout << "error: no matches found\n"; return 1; }
     const double focal_guess = (width + height) / 2, centerx = width / 2, centery = height / 2;     // :101-103 (integer division as in the reference)
+    if (match_mode ? !read_features(output, keyframes) : (!read_feature_tracks(output, keyframes, image_matches) || image_matches.empty())) { std::cout << "error: no matches found\n"; return 1; }
     std::cout << "initial focal: " << focal_guess << "\n";
     const double min_focal = focal_guess / 4, max_focal = focal_guess * 2;                          // :141-142
 
-    SfM sfm_probe(Intrinsics(focal_guess, centerx, centery));                                       // owns the library context for the search
+    SfM sfm_probe(Intrinsics(focal_guess, centerx, centery));                                       // owns the library context for the pairwise stage and the search
+    int loop_closures = -1;
+    if (match_mode) {                                                                               // :96-122
+        loop_closures = estimate_pairwise_from_features(sfm_probe.GetContext(), Intrinsics(focal_guess, centerx, centery), keyframes, inlierthresh, mininliers, inward, image_matches);
+        if (loop_closures == 0) { std::cout << "error: no loop closures found\n"; return 1; }
+        find_largest_connected_component(keyframes, image_matches);
+        if (image_matches.empty()) { std::cout << "error: no matches found\n"; return 1; }
+    }
     std::vector<Mat3> rotations; double focal_new = focal_guess;
     if (!find_best_focal_length_random(sfm_probe.GetContext(), (int)keyframes.size(), image_matches, inward, true, focal_guess, min_focal, max_focal,
                                        num_trials, rotations, focal_new, seed, (output + "/costs.txt").c_str())) {
@@ -74,6 +88,7 @@ int main(int argc, char** argv) {
     sfm.WriteCameraCentersOBJ(output + "/cameras.obj");
     sfm.WriteCOLMAP(output + "/sparse", width, height);
     sfm.WriteCalib(output + "/calib.txt");
+    std::printf("PAIRWISE_RESULT pairs=%zu loop_closures=%d\n", image_matches.size(), loop_closures);
     std::printf("PIPELINE_RESULT ok=%d%d%d%d cameras=%d focal_guess=%.3f focal_search=%.6f focal_spherical=%.6f focal_final=%.6f cost=%.6e residuals=%lld\n", ok1, ok2, ok3, ok4,
                 sfm.GetNumCameras(), focal_guess, focal_search, focal_spherical, sfm.GetFocal(), sfm.LastSummary().final_cost, (long long)sfm.LastSummary().num_residual_blocks);
     return 0;

@@ -1,5 +1,6 @@
 // see tools.h
 #include "tools.h"
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -8,78 +9,6 @@
 #include "../ssfm_math.h"
 
 namespace sphericalsfm {
-
-void write_feature_tracks(const std::string& outputpath, const std::vector<Keyframe>& keyframes, const std::vector<ImageMatch>& image_matches) {
-    if (FILE* f = std::fopen((outputpath + "/keyframes.txt").c_str(), "w")) {
-        std::fprintf(f, "%d\n", (int)keyframes.size());
-        for (const Keyframe& k : keyframes) std::fprintf(f, "%d %s\n", k.index, k.name.c_str());
-        std::fclose(f);
-    }
-    if (FILE* f = std::fopen((outputpath + "/features.dat").c_str(), "w")) {
-        for (const Keyframe& k : keyframes) {
-            const int nfeatures = k.features.size();
-            std::fwrite(&nfeatures, sizeof(int), 1, f);
-            for (int j = 0; j < nfeatures; j++) {
-                std::fwrite(&k.features.points[j].x, sizeof(float), 1, f); std::fwrite(&k.features.points[j].y, sizeof(float), 1, f);
-                static const float zeros[128] = {0};
-                std::fwrite(k.features.descs.size() >= (size_t)(j + 1) * 128 ? &k.features.descs[(size_t)j * 128] : zeros, sizeof(float), 128, f);
-            }
-        }
-        std::fclose(f);
-    }
-    if (FILE* f = std::fopen((outputpath + "/matches.dat").c_str(), "w")) {
-        const int n = (int)image_matches.size(); std::fwrite(&n, sizeof(int), 1, f);
-        for (const ImageMatch& m : image_matches) {
-            std::fwrite(&m.index0, sizeof(int), 1, f); std::fwrite(&m.index1, sizeof(int), 1, f);
-            const int nm = (int)m.matches.size(); std::fwrite(&nm, sizeof(int), 1, f);
-            for (auto& kv : m.matches) { const int a = (int)kv.first, b = (int)kv.second; std::fwrite(&a, sizeof(int), 1, f); std::fwrite(&b, sizeof(int), 1, f); }
-            std::fwrite(m.R.data(), sizeof(double), 9, f);                              // Eigen column-major
-        }
-        std::fclose(f);
-    }
-}
-
-bool read_feature_tracks(const std::string& outputpath, std::vector<Keyframe>& keyframes, std::vector<ImageMatch>& image_matches) {
-    FILE* kf = std::fopen((outputpath + "/keyframes.txt").c_str(), "r");
-    if (!kf) return false;
-    int nkeyframes = 0;
-    if (std::fscanf(kf, "%d\n", &nkeyframes) != 1 || nkeyframes < 0) { std::fclose(kf); return false; }
-    std::vector<int> indices(nkeyframes);
-    for (int i = 0; i < nkeyframes; i++) {
-        if (std::fscanf(kf, "%d", &indices[i]) != 1) { std::fclose(kf); return false; }
-        int ch; while ((ch = std::fgetc(kf)) != EOF && ch != '\n') {}                  // the rest of the line is the name
-    }
-    std::fclose(kf);
-    std::cout << "read " << indices.size() << " indices\n";
-    FILE* ff = std::fopen((outputpath + "/features.dat").c_str(), "r");
-    if (!ff) return false;
-    for (int i = 0; i < nkeyframes; i++) {
-        int nfeatures = 0;
-        if (std::fread(&nfeatures, sizeof(int), 1, ff) != 1 || nfeatures < 0) { std::fclose(ff); return false; }
-        Features features; features.points.resize(nfeatures); features.descs.resize((size_t)nfeatures * 128);
-        for (int j = 0; j < nfeatures; j++) {
-            if (std::fread(&features.points[j].x, sizeof(float), 1, ff) != 1 || std::fread(&features.points[j].y, sizeof(float), 1, ff) != 1 ||
-                std::fread(&features.descs[(size_t)j * 128], sizeof(float), 128, ff) != 128) { std::fclose(ff); return false; }
-        }
-        char name[1024]; std::snprintf(name, sizeof name, "%06d.jpg", indices[i] + 1);
-        keyframes.push_back(Keyframe(indices[i], name, features));
-    }
-    std::fclose(ff);
-    FILE* mf = std::fopen((outputpath + "/matches.dat").c_str(), "r");
-    if (!mf) return false;
-    int nmatches = 0;
-    if (std::fread(&nmatches, sizeof(int), 1, mf) != 1) { std::fclose(mf); return false; }
-    for (int i = 0; i < nmatches; i++) {
-        int index0, index1, nm;
-        if (std::fread(&index0, sizeof(int), 1, mf) != 1 || std::fread(&index1, sizeof(int), 1, mf) != 1 || std::fread(&nm, sizeof(int), 1, mf) != 1) { std::fclose(mf); return false; }
-        Matches m;
-        for (int j = 0; j < nm; j++) { int a, b; if (std::fread(&a, sizeof(int), 1, mf) != 1 || std::fread(&b, sizeof(int), 1, mf) != 1) { std::fclose(mf); return false; } m[a] = b; }
-        Mat3 R; if (std::fread(R.data(), sizeof(double), 9, mf) != 9) { std::fclose(mf); return false; }
-        image_matches.push_back(ImageMatch(index0, index1, m, R));
-    }
-    std::fclose(mf);
-    return true;
-}
 
 int estimate_pairwise(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, const std::vector<ImageMatch>& image_matches,
                       double inlier_threshold, int min_num_inliers, bool inward, std::vector<ImageMatch>& image_matches_out) {
@@ -130,6 +59,100 @@ int estimate_pairwise(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::ve
         Mat3 Rk; for (int q = 0; q < 9; q++) Rk[q] = R[9 * (size_t)k + q];
         if (cand[k]->index0 + 1 != cand[k]->index1) loop_closure_count++;
         image_matches_out.push_back(ImageMatch(cand[k]->index0, cand[k]->index1, inl, Rk));
+    }
+    return loop_closure_count;
+}
+
+// per-frame tables of the C ABI: feat_ptr, descriptors (128 floats per feature), optionally the rays Kinv (x, y, 1)
+static void feature_tables(const std::vector<const Features*>& fs, const Intrinsics* intrinsics, std::vector<int32_t>& feat_ptr, std::vector<float>& descs, std::vector<double>* rays) {
+    const int nf = (int)fs.size();
+    feat_ptr.assign(nf + 1, 0);
+    for (int f = 0; f < nf; f++) feat_ptr[f + 1] = feat_ptr[f] + (int32_t)fs[f]->points.size();
+    descs.assign((size_t)128 * std::max(1, (int)feat_ptr[nf]), 0.0f);
+    if (rays) rays->assign((size_t)3 * std::max(1, (int)feat_ptr[nf]), 0.0);
+    for (int f = 0; f < nf; f++) {
+        const Features& ft = *fs[f];
+        const size_t n = ft.points.size(), have = std::min(n, ft.descs.size() / 128);
+        if (have) std::copy(ft.descs.begin(), ft.descs.begin() + have * 128, descs.begin() + (size_t)feat_ptr[f] * 128);
+        if (rays) {
+            const double kinv = 1.0 / intrinsics->focal;
+            for (size_t k = 0; k < n; k++) {
+                double* r = &(*rays)[3 * ((size_t)feat_ptr[f] + k)];
+                r[0] = (ft.points[k].x - intrinsics->centerx) * kinv; r[1] = (ft.points[k].y - intrinsics->centery) * kinv; r[2] = 1.0;
+            }
+        }
+    }
+}
+
+static void exhaustive_pairs(const std::vector<Keyframe>& keyframes, std::vector<int32_t>& pf0, std::vector<int32_t>& pf1) {
+    for (size_t a = 0; a < keyframes.size(); a++) for (size_t b = a + 1; b < keyframes.size(); b++) { pf0.push_back((int32_t)a); pf1.push_back((int32_t)b); }   // :577-586
+}
+
+static void match_lists(ssfm_ctx* ctx, const std::vector<const Features*>& fs, const std::vector<int32_t>& pf0, const std::vector<int32_t>& pf1, double ratio,
+                        std::vector<int32_t>& mp, std::vector<int32_t>& m0, std::vector<int32_t>& m1) {
+    std::vector<int32_t> feat_ptr; std::vector<float> descs;
+    feature_tables(fs, nullptr, feat_ptr, descs, nullptr);
+    ssfm_match_options O; ssfm_match_default_options(&O); O.ratio = ratio;
+    const int P = (int)pf0.size();
+    mp.assign(P + 1, 0);
+    int64_t cap = 0;
+    for (int p = 0; p < P; p++) cap += std::min(feat_ptr[pf0[p] + 1] - feat_ptr[pf0[p]], feat_ptr[pf1[p] + 1] - feat_ptr[pf1[p]]);       // a pair has at most min(n0, n1) matches
+    m0.assign((size_t)std::max<int64_t>(cap, 1), 0); m1.assign((size_t)std::max<int64_t>(cap, 1), 0);
+    if (ssfm_match_pairs(ctx, (int32_t)fs.size(), feat_ptr.data(), descs.data(), P, pf0.data(), pf1.data(), &O, cap, mp.data(), m0.data(), m1.data()) != SSFM_OK) {
+        std::cout << "error: " << ssfm_last_error(ctx) << "\n"; std::exit(1);
+    }
+}
+
+void match(ssfm_ctx* ctx, const Features& features0, const Features& features1, Matches& m01, double ratio) {
+    std::vector<int32_t> mp, m0, m1;
+    match_lists(ctx, {&features0, &features1}, {0}, {1}, ratio, mp, m0, m1);
+    for (int32_t k = mp[0]; k < mp[1]; k++) m01[(size_t)m0[k]] = (size_t)m1[k];
+}
+
+void match_exhaustive(ssfm_ctx* ctx, const std::vector<Keyframe>& keyframes, std::vector<ImageMatch>& image_matches) {
+    if (keyframes.size() < 2) return;
+    std::vector<const Features*> fs; for (const Keyframe& k : keyframes) fs.push_back(&k.features);
+    std::vector<int32_t> pf0, pf1, mp, m0, m1;
+    exhaustive_pairs(keyframes, pf0, pf1);
+    match_lists(ctx, fs, pf0, pf1, 0.75, mp, m0, m1);
+    const Mat3 I = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    for (size_t p = 0; p < pf0.size(); p++) {                                             // every pair is stored, also one without a match (:577-586), under its POSITIONS
+        Matches m; for (int32_t k = mp[p]; k < mp[p + 1]; k++) m[(size_t)m0[k]] = (size_t)m1[k];
+        image_matches.push_back(ImageMatch(pf0[p], pf1[p], m, I));
+    }
+}
+
+int estimate_pairwise_from_features(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, double inlier_threshold, int min_num_inliers,
+                                    bool inward, std::vector<ImageMatch>& image_matches_out) {
+    if (keyframes.size() < 2) return 0;
+    const double kinv = 1.0 / intrinsics.focal;
+    const double sq_thresh = inlier_threshold * inlier_threshold * kinv * kinv;           // :315
+    std::vector<const Features*> fs; for (const Keyframe& k : keyframes) fs.push_back(&k.features);
+    std::vector<int32_t> feat_ptr, pf0, pf1; std::vector<float> descs; std::vector<double> rays;
+    feature_tables(fs, &intrinsics, feat_ptr, descs, &rays);
+    exhaustive_pairs(keyframes, pf0, pf1);
+    ssfm_ransac_options O; ssfm_ransac_default_options(&O);
+    O.min_num_inliers = min_num_inliers; O.inward = inward ? 1 : 0; O.final_least_squares = 1;                                 // :316-318
+    const int P = (int)pf0.size();
+    int64_t pair_cap = P, inl_cap = 0, needed[2] = {0, 0};
+    for (int p = 0; p < P; p++) inl_cap += std::min(feat_ptr[pf0[p] + 1] - feat_ptr[pf0[p]], feat_ptr[pf1[p] + 1] - feat_ptr[pf1[p]]);   // a pair has at most min(n0, n1) matches: never a miss
+    std::vector<int32_t> acc, nin, ptr, i0, i1; std::vector<double> R;
+    for (int attempt = 0; attempt < 2; attempt++) {                                       // the capacity protocol (the bounds above cannot miss; a retry would repeat all the work)
+        acc.assign((size_t)std::max<int64_t>(pair_cap, 1), 0); nin.assign(acc.size(), 0); ptr.assign((size_t)pair_cap + 1, 0); R.assign(9 * acc.size(), 0.0);
+        i0.assign((size_t)std::max<int64_t>(inl_cap, 1), 0); i1.assign(i0.size(), 0);
+        const int rc = ssfm_pairwise_from_features(ctx, (int32_t)fs.size(), feat_ptr.data(), descs.data(), rays.data(), P, pf0.data(), pf1.data(), nullptr, &O, sq_thresh,
+                                                   pair_cap, inl_cap, needed, acc.data(), R.data(), nin.data(), ptr.data(), i0.data(), i1.data(), nullptr, nullptr, nullptr);
+        if (rc == SSFM_OK) break;
+        if (attempt == 0 && (needed[0] > pair_cap || needed[1] > inl_cap)) { pair_cap = needed[0]; inl_cap = needed[1]; continue; }
+        std::cout << "error: " << ssfm_last_error(ctx) << "\n"; std::exit(1);
+    }
+    int loop_closure_count = 0;
+    for (int64_t a = 0; a < needed[0]; a++) {
+        const int index0 = pf0[acc[a]], index1 = pf1[acc[a]];                             // positions in `keyframes`, as estimate_pairwise reads ImageMatch::index0 / index1
+        Matches inl; for (int32_t k = ptr[a]; k < ptr[a + 1]; k++) inl[(size_t)i0[k]] = (size_t)i1[k];
+        Mat3 Rk; for (int q = 0; q < 9; q++) Rk[q] = R[9 * (size_t)a + q];
+        if (index0 + 1 != index1) loop_closure_count++;
+        image_matches_out.push_back(ImageMatch(index0, index1, inl, Rk));
     }
     return loop_closure_count;
 }

@@ -49,6 +49,29 @@ bool read_feature_tracks(const std::string& outputpath, std::vector<Keyframe>& k
 int estimate_pairwise(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, const std::vector<ImageMatch>& image_matches,
                       double inlier_threshold, int min_num_inliers, bool inward, std::vector<ImageMatch>& image_matches_out);
 
+// match (spherical_sfm_tools.cpp:235-251) and match_exhaustive (:575-600) over ssfm_match_pairs: features0 is the train set, features1 the query set, m01 maps a
+// feature of features0 to the LAST query that chose it; match_exhaustive appends one ImageMatch per pair index0 < index1 -- every pair, also one without a match,
+// as the reference does -- where index0 / index1 are the POSITIONS in `keyframes` (the reference's loop counters; what estimate_pairwise,
+// find_largest_connected_component, initialize_rotations_sequential and build_sfm read them as), not Keyframe::index.  Its rotation is the identity (the
+// reference leaves it uninitialised).  The reference's signatures plus the context argument.
+void match(ssfm_ctx* ctx, const Features& features0, const Features& features1, Matches& m01, double ratio = 0.75);
+void match_exhaustive(ssfm_ctx* ctx, const std::vector<Keyframe>& keyframes, std::vector<ImageMatch>& image_matches);
+
+// find_largest_connected_component (:736-792), on the host with union-find: the vertices are 0 .. the largest index an edge names, components are numbered in order
+// of their smallest vertex, the first largest one wins a tie; keyframes and matches of that component are kept and renumbered in place (Keyframe::index keeps the
+// original frame number).  DEFINED here: keyframes beyond the last vertex that any edge names are in no component and are dropped (the reference reads its
+// component table out of range for them); with no edges at all everything is dropped.
+void find_largest_connected_component(std::vector<Keyframe>& keyframes, std::vector<ImageMatch>& image_matches);
+
+// keyframes.txt + features.dat without matches.dat
+bool read_features(const std::string& outputpath, std::vector<Keyframe>& keyframes);
+
+// match_exhaustive + estimate_pairwise in one device call (ssfm_pairwise_from_features) for all pairs index0 < index1 of keyframes[index]: the match lists never come
+// back to the host, only the accepted pairs' inlier matches and rotations do.  Same result and return value as match_exhaustive followed by estimate_pairwise.
+// Single-GPU: the context must not carry a communicator.
+int estimate_pairwise_from_features(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, double inlier_threshold, int min_num_inliers,
+                                    bool inward, std::vector<ImageMatch>& image_matches_out);
+
 void initialize_rotations_sequential(int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations);   // tools.cpp:794-813
 double refine_rotations(ssfm_ctx* ctx, int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations); // tools.cpp:851-860
 // tools.cpp:862-955: tracks (ssfm_build_tracks, ids bit-exact with the reference's AddPoint sequence), cameras, observations, Retriangulate
