@@ -425,6 +425,49 @@ int ssfm_focal_search(ssfm_ctx* ctx, int32_t n, int32_t num_edges, const int32_t
                       const double* rel_rotations, int32_t inward, double focal_guess, int32_t num_trials, const double* focals,
                       double* costs, int32_t* best_trial, double* rotations_best, double* rel_rotations_best);
 
+/* ---- general view graphs: unordered image sets (the sequential == false branch, examples/run_spherical_sfm.cpp:73-76) -----------
+ * The edge list is what estimate_pairwise leaves: edge e = (index0[e], index1[e]) carries rel_rotations[9 e ..], column-major, with the
+ * convention of the whole code base R_index1 = R_e R_index0.  All three calls are single-GPU: a context with a communicator is refused
+ * (SSFM_ERR_INVALID).
+ *
+ * ssfm_triplet_filter: filter_image_matches (examples/spherical_sfm_tools.cpp:1031-1082) as a sparse join on the device.  A triplet is an
+ *   ordered triple of LIST POSITIONS (i, j, k) with index1[i] == index0[j], index0[k] == index0[i], index1[k] == index1[j] -- the reference's
+ *   three loops literally: no distinctness test, so duplicate edges, self loops and edges with index0 > index1 take part as they do there.
+ *   err < err_thresh_rad (fp64, strict) sets good_out[i] = good_out[j] = good_out[k] = 1; every other entry is 0.  *num_triplets_out counts
+ *   every triplet.  The result depends on the inputs alone (idempotent flags, integer counts, no floating-point sum across lanes).
+ *   order: which product the error is taken of --
+ *     SSFM_TRIPLET_ORDER_REFERENCE  |so3ln(Rij Rjk Rik^T)|  spherical_sfm_tools.cpp:1055 as written
+ *     SSFM_TRIPLET_ORDER_COMPOSED   |so3ln(Rjk Rij Rik^T)|  what R_b = R_ab R_a implies: a consistent triangle has Rik = Rjk Rij
+ *   The two agree only where the rotations commute (nearly so for the one-axis motion of a spherical capture).
+ *   Records: if triplet_edges_out is not NULL (then triplet_err_out must not be either), the first min(num_triplets, max_records) triplets are
+ *   written, (i, j, k) as list positions and err in radians, in THIS order: i ascending; within an i, j ascending by (index1[j], j); within a
+ *   j, k ascending.  For a list sorted by (index0, index1) -- what estimate_pairwise produces from match_exhaustive -- that is the order of
+ *   the lines of the reference's filter.txt.  Nothing is written past max_records.
+ *   An index outside [0, num_cameras) gives SSFM_ERR_INVALID before anything is launched; num_edges == 0 is valid.
+ *
+ * ssfm_view_graph_tree (host only, no context): breadth-first spanning tree from `root`.  A popped node scans its incident edges in
+ *   ascending list position and adopts every neighbour not seen yet.  Output in visiting order (= level order), num_reached entries:
+ *   node_out[0] = root with parent_out / edge_out = -1; reversed_out = 1 when the tree edge is stored as (child, parent);
+ *   level l = positions level_ptr[l] .. level_ptr[l + 1], l < *num_levels.  Self loops and duplicates are harmless; unreached cameras are not
+ *   listed.  Arrays hold num_cameras entries (level_ptr num_cameras + 1); the rest is filled with -1 (reversed 0, level_ptr num_reached).
+ *
+ * ssfm_focal_search_graph: ssfm_focal_search with the same transform_image_matches step, the same get_cost and the same first-minimum
+ *   rule, but the rotations of every trial are chained along the tree of ssfm_view_graph_tree(root), built once per call: a forward tree
+ *   edge gives R_child = R_e R_parent, a reversed one R_child = R_e^T R_parent, unreached cameras keep the identity.  One workgroup per
+ *   trial walks the tree level by level.  This is the project's own initialisation for a graph without a chain; the reference's
+ *   initialize_rotations_gopt (GraphOptim, third party) is not restated. */
+#define SSFM_TRIPLET_ORDER_REFERENCE 0
+#define SSFM_TRIPLET_ORDER_COMPOSED 1
+int ssfm_triplet_filter(ssfm_ctx* ctx, int32_t num_cameras, int32_t num_edges, const int32_t* index0, const int32_t* index1,
+                        const double* rel_rotations, double err_thresh_rad, int32_t order, uint8_t* good_out, int64_t* num_triplets_out,
+                        int64_t max_records, int32_t* triplet_edges_out, double* triplet_err_out);
+int ssfm_view_graph_tree(int32_t num_cameras, int32_t num_edges, const int32_t* index0, const int32_t* index1, int32_t root,
+                         int32_t* num_reached, int32_t* node_out, int32_t* parent_out, int32_t* edge_out, uint8_t* reversed_out,
+                         int32_t* num_levels, int32_t* level_ptr);
+int ssfm_focal_search_graph(ssfm_ctx* ctx, int32_t n, int32_t num_edges, const int32_t* index0, const int32_t* index1,
+                            const double* rel_rotations, int32_t inward, double focal_guess, int32_t num_trials, const double* focals,
+                            int32_t root, double* costs, int32_t* best_trial, double* rotations_best, double* rel_rotations_best);
+
 /* ---- SfM::Retriangulate (src/sfm.cpp:156-192) ------------------------------------------------------------------
  * Re-estimates EVERY point of the problem from its observations and the current cameras/focal with the per-point
  * ransac_lib::LocallyOptimizedMSAC<Point, ..., TriangulationEstimator> of the reference (src/triangulation_estimator.cpp:46-127,

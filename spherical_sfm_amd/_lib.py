@@ -93,6 +93,7 @@ DECLARED_SYMBOLS = [
     "ssfm_estimator_evaluate_model", "ssfm_estimator_least_squares", "ssfm_estimator_decompose",
     "ssfm_match_default_options", "ssfm_match_pairs", "ssfm_match_knn_probe", "ssfm_match_last_kernel_ms",
     "ssfm_pairwise_from_features", "ssfm_pairwise_front_last_kernel_ms",
+    "ssfm_triplet_filter", "ssfm_view_graph_tree", "ssfm_focal_search_graph",
 ]
 
 
@@ -195,6 +196,13 @@ def lib():
                                               C.c_double, C.c_int64, C.c_int64, c_i64_p, c_i32_p, c_double_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_u32_p]
     L.ssfm_pairwise_from_features.restype = C.c_int
     L.ssfm_pairwise_front_last_kernel_ms.argtypes = [vp, c_double_p]; L.ssfm_pairwise_front_last_kernel_ms.restype = C.c_int
+    L.ssfm_triplet_filter.argtypes = [vp, C.c_int32, C.c_int32, c_i32_p, c_i32_p, c_double_p, C.c_double, C.c_int32, c_u8_p, c_i64_p, C.c_int64, c_i32_p, c_double_p]
+    L.ssfm_triplet_filter.restype = C.c_int
+    L.ssfm_view_graph_tree.argtypes = [C.c_int32, C.c_int32, c_i32_p, c_i32_p, C.c_int32, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_u8_p, c_i32_p, c_i32_p]
+    L.ssfm_view_graph_tree.restype = C.c_int
+    L.ssfm_focal_search_graph.argtypes = [vp, C.c_int32, C.c_int32, c_i32_p, c_i32_p, c_double_p, C.c_int32, C.c_double, C.c_int32, c_double_p, C.c_int32, c_double_p,
+                                          c_i32_p, c_double_p, c_double_p]
+    L.ssfm_focal_search_graph.restype = C.c_int
     _LIB = L
     return L
 

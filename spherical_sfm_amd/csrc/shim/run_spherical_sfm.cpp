@@ -5,7 +5,13 @@
 // Feature detection over images (the OpenCV front end) is outside this build.  With -match the driver starts from keyframes.txt + features.dat alone, as the
 // reference's driver does after detect_features (:49-55): match_exhaustive + estimate_pairwise in one device call (estimate_pairwise_from_features), then
 // find_largest_connected_component.  Without it, it starts from a matches.dat (-pairwise: that file holds raw matches, estimate_pairwise runs first).
+// -viewgraph: the frames need not be in capture order (the reference's sequential == false branch, :73-76): filter_image_matches(2 degrees) on the device, then
+// find_largest_connected_component AGAIN -- the filter can split the graph; the reference does not guard against that, this driver does -- then the rotations chained
+// along a breadth-first spanning tree (initialize_rotations_tree, in place of GraphOptim) and the same rotation averaging.  -tripletorder composed selects the product
+// order that the edge convention implies instead of the reference's (include/ssfm.h).  Without -viewgraph nothing changes.
 //   run_spherical_sfm -intrinsics <file: focal cx cy> -output <dir with the feature tracks> [-match | -pairwise] [-inward] [-width W -height H]
+//                     [-viewgraph [-tripletorder reference|composed]]
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -14,7 +20,7 @@
 using namespace sphericalsfm;
 
 int main(int argc, char** argv) {
-    std::string intrinsics_path, output; bool inward = false, pairwise = false, match_mode = false; int width = 1920, height = 1080, mininliers = 100; double inlierthresh = 2.0;
+    std::string intrinsics_path, output; bool inward = false, pairwise = false, match_mode = false, viewgraph = false; int triplet_order = SSFM_TRIPLET_ORDER_REFERENCE, width = 1920, height = 1080, mininliers = 100; double inlierthresh = 2.0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "-intrinsics" && i + 1 < argc) intrinsics_path = argv[++i];
@@ -26,7 +32,13 @@ int main(int argc, char** argv) {
         else if (a == "-match") match_mode = true;                          // no matches.dat: features -> verified image matches on the device
         else if (a == "-inlierthresh" && i + 1 < argc) inlierthresh = std::atof(argv[++i]);
         else if (a == "-mininliers" && i + 1 < argc) mininliers = std::atoi(argv[++i]);
-        else if (a == "-sequential") {}                                     // the only rotation initialisation available here
+        else if (a == "-sequential") viewgraph = false;                     // the default: rotations chained over the matches (k-1, k)
+        else if (a == "-viewgraph") viewgraph = true;                       // any pair may carry a rotation: triplet filter + spanning-tree initialisation
+        else if (a == "-tripletorder" && i + 1 < argc) {
+            const std::string o = argv[++i];
+            if (o == "composed") triplet_order = SSFM_TRIPLET_ORDER_COMPOSED; else if (o == "reference") triplet_order = SSFM_TRIPLET_ORDER_REFERENCE;
+            else { std::cout << "unknown triplet order " << o << "\n"; return 2; }
+        }
         else { std::cout << "unknown argument " << a << "\n"; return 2; }
     }
     if (intrinsics_path.empty() || output.empty()) { std::cout << "usage: run_spherical_sfm -intrinsics <file> -output <dir> [-inward]\n"; return 2; }
@@ -59,9 +71,18 @@ int main(int argc, char** argv) {
         if (loop_closures == 0) { std::cout << "error: no loop closures found\n"; return 1; }
         std::cout << "kept " << image_matches.size() << " of " << all_image_matches.size() << " image pairs, " << loop_closures << " loop closures\n";
     }
+    if (viewgraph) {                                                         // run_spherical_sfm.cpp:73-76
+        std::cout << "filtering image matches\n";
+        const size_t nframes = keyframes.size(), nmatches = image_matches.size();
+        image_matches = filter_image_matches(sfm.GetContext(), image_matches, 2.0 * M_PI / 180.0, triplet_order);
+        if (image_matches.empty()) { std::cout << "error: no image match survived the triplet filter\n"; return 1; }
+        find_largest_connected_component(keyframes, image_matches);          // the filter may have split the graph
+        std::cout << "after the triplet filter: " << keyframes.size() << " of " << nframes << " keyframes, " << image_matches.size() << " of " << nmatches << " image pairs\n";
+    }
     std::cout << "initializing rotations\n";
     std::vector<Mat3> rotations;
-    initialize_rotations_sequential((int)keyframes.size(), image_matches, rotations);
+    if (viewgraph) initialize_rotations_tree((int)keyframes.size(), image_matches, rotations);
+    else initialize_rotations_sequential((int)keyframes.size(), image_matches, rotations);
 
     std::cout << "refining rotations\n";
     const double rot_cost = refine_rotations(sfm.GetContext(), (int)keyframes.size(), image_matches, rotations);

@@ -5,8 +5,10 @@
 // Normalize; poses.txt, OBJ files, COLMAP text model, calib.txt.  Everything numerical runs in libssfm_hip.so.
 // -match: no matches.dat -- match_exhaustive + estimate_pairwise at the guessed focal in one device call (estimate_pairwise_from_features), then
 // find_largest_connected_component (:96-122).
+// -viewgraph: the frames need not be in capture order -- the focal search chains its trial rotations along a breadth-first spanning tree of the matches
+// (find_best_focal_length_random with sequential = false -> ssfm_focal_search_graph) instead of along the matches (k-1, k).  Without it nothing changes.
 //   run_spherical_sfm_uncalib -output <dir with keyframes.txt, features.dat, matches.dat> -width W -height H [-generalba] [-inward]
-//                             [-match [-inlierthresh T] [-mininliers N]]
+//                             [-match [-inlierthresh T] [-mininliers N]] [-viewgraph]
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -14,7 +16,7 @@
 using namespace sphericalsfm;
 
 int main(int argc, char** argv) {
-    std::string output; bool inward = false, generalba = false, match_mode = false; int width = 0, height = 0, num_trials = 1024, mininliers = 100; unsigned seed = 0; double inlierthresh = 2.0;
+    std::string output; bool inward = false, generalba = false, match_mode = false, viewgraph = false; int width = 0, height = 0, num_trials = 1024, mininliers = 100; unsigned seed = 0; double inlierthresh = 2.0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "-output" && i + 1 < argc) output = argv[++i];
@@ -27,7 +29,8 @@ int main(int argc, char** argv) {
         else if (a == "-match") match_mode = true;
         else if (a == "-inlierthresh" && i + 1 < argc) inlierthresh = std::atof(argv[++i]);
         else if (a == "-mininliers" && i + 1 < argc) mininliers = std::atoi(argv[++i]);
-        else if (a == "-sequential") {}
+        else if (a == "-sequential") viewgraph = false;
+        else if (a == "-viewgraph") viewgraph = true;
         else { std::cout << "unknown argument " << a << "\n"; return 2; }
     }
     if (output.empty() || width <= 0 || height <= 0) { std::cout << "usage: run_spherical_sfm_uncalib -output <dir> -width W -height H [-generalba] [-inward]\n"; return 2; }
@@ -46,7 +49,7 @@ int main(int argc, char** argv) {
         if (image_matches.empty()) { std::cout << "error: no matches found\n"; return 1; }
     }
     std::vector<Mat3> rotations; double focal_new = focal_guess;
-    if (!find_best_focal_length_random(sfm_probe.GetContext(), (int)keyframes.size(), image_matches, inward, true, focal_guess, min_focal, max_focal,
+    if (!find_best_focal_length_random(sfm_probe.GetContext(), (int)keyframes.size(), image_matches, inward, !viewgraph, focal_guess, min_focal, max_focal,
                                        num_trials, rotations, focal_new, seed, (output + "/costs.txt").c_str())) {
         std::cout << "ERROR: could not find any acceptable focal length\n"; return 1;
     }

@@ -171,6 +171,45 @@ void initialize_rotations_sequential(int num_cameras, const std::vector<ImageMat
             }
 }
 
+std::vector<ImageMatch> filter_image_matches(ssfm_ctx* ctx, std::vector<ImageMatch>& image_matches, double err_thresh_rad, int order, const char* log_path) {
+    const int E = (int)image_matches.size();
+    int num_cameras = 0;
+    std::vector<int32_t> i0(E), i1(E); std::vector<double> rel((size_t)9 * E);
+    for (int e = 0; e < E; e++) {
+        i0[e] = image_matches[e].index0; i1[e] = image_matches[e].index1; num_cameras = std::max(num_cameras, std::max(i0[e], i1[e]) + 1);
+        for (int k = 0; k < 9; k++) rel[9 * (size_t)e + k] = image_matches[e].R[k];
+    }
+    std::vector<uint8_t> good((size_t)E, 0); int64_t num_triplets = 0;
+    std::vector<int32_t> tri; std::vector<double> err;
+    for (int pass = 0; pass < (log_path ? 2 : 1); pass++) {                               // the log needs the count first: with a log_path the WHOLE call runs twice (filter kernel included), the second time asking for that many records
+        if (pass == 1) { tri.assign((size_t)std::max<int64_t>(3 * num_triplets, 1), 0); err.assign((size_t)std::max<int64_t>(num_triplets, 1), 0.0); }
+        if (ssfm_triplet_filter(ctx, num_cameras, E, i0.data(), i1.data(), rel.data(), err_thresh_rad, order, good.data(), &num_triplets, pass ? num_triplets : 0,
+                                pass ? tri.data() : nullptr, pass ? err.data() : nullptr) != SSFM_OK) {
+            std::cout << "error: " << ssfm_last_error(ctx) << "\n"; std::exit(1);
+        }
+    }
+    return apply_triplet_filter(image_matches, good, log_path ? num_triplets : 0, tri.data(), err.data(), log_path);
+}
+
+void initialize_rotations_tree(int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations, int root) {
+    const Mat3 I = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    rotations.assign(std::max(num_cameras, 0), I);
+    const int E = (int)image_matches.size();
+    if (num_cameras <= 0) return;
+    std::vector<int32_t> i0(E), i1(E), node(num_cameras), parent(num_cameras), edge(num_cameras), level_ptr((size_t)num_cameras + 1); std::vector<uint8_t> rev(num_cameras);
+    for (int e = 0; e < E; e++) { i0[e] = image_matches[e].index0; i1[e] = image_matches[e].index1; }
+    int32_t reached = 0, levels = 0;
+    if (ssfm_view_graph_tree(num_cameras, E, i0.data(), i1.data(), root, &reached, node.data(), parent.data(), edge.data(), rev.data(), &levels, level_ptr.data()) != SSFM_OK) {
+        std::cout << "error: " << ssfm_last_error(nullptr) << "\n"; std::exit(1);
+    }
+    for (int k = 1; k < reached; k++) {                                                   // column-major 3x3: R_child = R_e R_parent, or R_e^T R_parent for an edge stored (child, parent)
+        const Mat3& Re = image_matches[edge[k]].R; const Mat3& Rp = rotations[parent[k]];
+        Mat3 Rn;
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) { double s = 0; for (int q = 0; q < 3; q++) s += (rev[k] ? Re[q + 3 * r] : Re[r + 3 * q]) * Rp[q + 3 * c]; Rn[r + 3 * c] = s; }
+        rotations[node[k]] = Rn;
+    }
+}
+
 double refine_rotations(ssfm_ctx* ctx, int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations) {
     const int E = (int)image_matches.size();
     std::vector<int32_t> i0(E), i1(E); std::vector<double> rel((size_t)9 * E), rot((size_t)9 * num_cameras);
@@ -225,7 +264,6 @@ void build_sfm(std::vector<Keyframe>& keyframes, const std::vector<ImageMatch>& 
 bool find_best_focal_length_random(ssfm_ctx* ctx, int num_cameras, std::vector<ImageMatch>& image_matches, bool inward, bool sequential,
                                    double focal_guess, double min_focal, double max_focal, int num_trials, std::vector<Mat3>& rotations,
                                    double& best_focal, unsigned seed, const char* costs_path) {
-    if (!sequential) { std::cout << "error: only the sequential rotation initialisation is available\n"; return false; }
     const int E = (int)image_matches.size();
     std::vector<int32_t> i0(E), i1(E); std::vector<double> rel((size_t)9 * E);
     for (int e = 0; e < E; e++) { i0[e] = image_matches[e].index0; i1[e] = image_matches[e].index1; for (int k = 0; k < 9; k++) rel[9 * (size_t)e + k] = image_matches[e].R[k]; }
@@ -235,8 +273,11 @@ bool find_best_focal_length_random(ssfm_ctx* ctx, int num_cameras, std::vector<I
     for (int t = 0; t < num_trials; t++) focals[t] = dist(gen);
     int32_t best = 0;
     std::vector<double> rot((size_t)9 * num_cameras), rel_best((size_t)9 * E);
-    if (ssfm_focal_search(ctx, num_cameras, E, i0.data(), i1.data(), rel.data(), inward ? 1 : 0, focal_guess, num_trials, focals.data(), costs.data(),
-                          &best, rot.data(), rel_best.data()) != SSFM_OK) { std::cout << "error: " << ssfm_last_error(ctx) << "\n"; return false; }
+    const int rc = sequential ? ssfm_focal_search(ctx, num_cameras, E, i0.data(), i1.data(), rel.data(), inward ? 1 : 0, focal_guess, num_trials, focals.data(), costs.data(),
+                                                  &best, rot.data(), rel_best.data())
+                              : ssfm_focal_search_graph(ctx, num_cameras, E, i0.data(), i1.data(), rel.data(), inward ? 1 : 0, focal_guess, num_trials, focals.data(), 0,
+                                                        costs.data(), &best, rot.data(), rel_best.data());
+    if (rc != SSFM_OK) { std::cout << "error: " << ssfm_last_error(ctx) << "\n"; return false; }
     if (costs_path) {                                                                     // :1463-1468
         if (FILE* f = std::fopen(costs_path, "w")) { for (int t = 0; t < num_trials; t++) std::fprintf(f, "%d %lf %lf\n", t, focals[t], costs[t]); std::fclose(f); }
     }

@@ -78,10 +78,28 @@ double refine_rotations(ssfm_ctx* ctx, int num_cameras, const std::vector<ImageM
 void build_sfm(std::vector<Keyframe>& keyframes, const std::vector<ImageMatch>& image_matches, const std::vector<Mat3>& rotations, SfM& sfm,
                bool spherical, bool merge, bool inward, int fix_camera = 0);
 
+// filter_image_matches (spherical_sfm_tools.cpp:1031-1082) over ssfm_triplet_filter: every ordered triple of matches (i, j, k) with i = (a, b), j = (b, c), k = (a, c)
+// is a triplet; a triplet whose rotation error is below err_thresh_rad marks its three matches good; the good matches come back in list order.  order: which product
+// the error is taken of -- the reference's own Rij Rjk Rik^T (the default) or Rjk Rij Rik^T, which is what R_b = R_ab R_a implies (include/ssfm.h).  Prints the
+// reference's "good edges" line; the per-triplet lines of filter.txt ("%d %d %d %f": index0, index1 of match i, index1 of match j, degrees) are written only when
+// log_path is given (the reference always writes them, and prints each to stdout); the log costs a second run of the filter, because the number of records
+// has to be known before they can be asked for.  Single-GPU: the context must not carry a communicator.
+std::vector<ImageMatch> filter_image_matches(ssfm_ctx* ctx, std::vector<ImageMatch>& image_matches, double err_thresh_rad, int order = SSFM_TRIPLET_ORDER_REFERENCE,
+                                             const char* log_path = nullptr);
+// the host half of it (tools_host.cpp): the kept matches from the flags, the "good edges" line, the log from the records (num_records triples of list positions + radians)
+std::vector<ImageMatch> apply_triplet_filter(const std::vector<ImageMatch>& image_matches, const std::vector<uint8_t>& good, int64_t num_records,
+                                             const int32_t* triplet_edges, const double* triplet_err, const char* log_path);
+
+// Rotation initialisation over a general view graph, in place of the reference's initialize_rotations_gopt (GraphOptim, third party, not restated): the relative
+// rotations chained along the breadth-first spanning tree of ssfm_view_graph_tree(root) -- forward tree edge R_child = R_e R_parent, reversed R_child = R_e^T R_parent;
+// cameras the tree does not reach keep the identity.  The robust refine_rotations that follows does the averaging.  Host code.
+void initialize_rotations_tree(int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations, int root = 0);
+
 // The reference seeds std::mt19937 from std::random_device and draws inside an OpenMP loop; here the draw is sequential from
 // `seed` (deterministic), everything after it follows the reference: costs of all trials in one GPU launch, first minimum,
-// sequential rotations at the best focal, then the joint rotation + focal refinement.  Only sequential = true is supported
-// (the GraphOptim initialisation is outside the scope of this build).  Returns false on an error of the library.
+// the initial rotations at the best focal, then the joint rotation + focal refinement.  sequential = true chains the matches (k-1, k)
+// (ssfm_focal_search); sequential = false chains along the spanning tree from camera 0 (ssfm_focal_search_graph), where the reference
+// calls GraphOptim.  Returns false on an error of the library.
 bool find_best_focal_length_random(ssfm_ctx* ctx, int num_cameras, std::vector<ImageMatch>& image_matches, bool inward, bool sequential,
                                    double focal_guess, double min_focal, double max_focal, int num_trials, std::vector<Mat3>& rotations,
                                    double& best_focal, unsigned seed = 0, const char* costs_path = "costs.txt");

@@ -2,6 +2,7 @@
 // that it builds and runs (tests/native/front_tools_check.cpp) without libssfm_hip.so.
 #include "tools.h"
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <iostream>
 
@@ -82,6 +83,27 @@ bool read_feature_tracks(const std::string& outputpath, std::vector<Keyframe>& k
     }
     std::fclose(mf);
     return true;
+}
+
+std::vector<ImageMatch> apply_triplet_filter(const std::vector<ImageMatch>& image_matches, const std::vector<uint8_t>& good, int64_t num_records,
+                                             const int32_t* triplet_edges, const double* triplet_err, const char* log_path) {
+    const size_t E = image_matches.size();
+    if (log_path) {
+        if (FILE* f = std::fopen(log_path, "w")) {                                        // spherical_sfm_tools.cpp:1057
+            for (int64_t t = 0; t < num_records; t++) {
+                const int32_t i = triplet_edges[3 * t], j = triplet_edges[3 * t + 1];
+                if (i < 0 || j < 0 || (size_t)i >= E || (size_t)j >= E) continue;
+                std::fprintf(f, "%d %d %d %f\n", image_matches[(size_t)i].index0, image_matches[(size_t)i].index1, image_matches[(size_t)j].index1, triplet_err[t] * 180 / M_PI);
+            }
+            std::fclose(f);
+        }
+    }
+    int count = 0;
+    std::vector<ImageMatch> image_matches_new;
+    for (size_t i = 0; i < E && i < good.size(); i++)
+        if (good[i]) { count++; image_matches_new.push_back(image_matches[i]); }
+    std::cout << count << " / " << E << " good edges\n";                                  // :1079
+    return image_matches_new;
 }
 
 void find_largest_connected_component(std::vector<Keyframe>& keyframes, std::vector<ImageMatch>& image_matches) {
