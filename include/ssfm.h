@@ -294,6 +294,57 @@ int ssfm_ransac_batch_indexed_sharded(ssfm_ctx* ctx, int32_t num_frames, const i
 /* Measurement aid (the RANSAC leg is priced in FP64 flop/s of Sampson scoring, not GB/s): device time of the kernels of this context's last
  * ssfm_ransac_batch* call, summed over its slabs (hipEvent brackets on the solver stream; uploads and read-backs are outside).  No reference counterpart. */
 int ssfm_ransac_last_kernel_ms(ssfm_ctx* ctx, double* ms);
+/* ---- general relative pose: five-point LO-MSAC per image pair (examples/spherical_sfm_tools.cpp:433-573, `-fivepoint`) ----------------
+ * estimate_pairwise_five_point per pair: LocallyOptimizedMSAC over SteweniusEstimator (evaluation/five_point/stewenius_estimator.cpp) with the
+ * one-sided epipolar-line residual of FivePointEstimator::EvaluateModelOnPoint (five_point_estimator.cpp:115-125: line = E (u / u2),
+ * (v . line)^2 / (line0^2 + line1^2); v is not renormalised), inlier flags by residual < threshold, acceptance num_inliers > min_num_inliers,
+ * then PoseFromEssentialMatrix on the inliers (:15-113).  No spherical-motion assumption: R is a general rotation and t a unit translation
+ * (x1 = R x0 + t), R = identity and t = 0 where the pair is not accepted.  u, v, pair_ptr, E, inlier_mask, num_inliers, scores, stats and the
+ * slabs, random streams and ssfm_ransac_last_kernel_ms are those of ssfm_ransac_batch; t: [num_pairs*3].  Rays need a nonzero third component.
+ *
+ * Options: the struct of ssfm_ransac_batch as it is.  Used: seed, min_num_inliers, min_num_iterations, max_num_iterations,
+ * success_probability, threshold_multiplier, lo_starting_iterations, fast_shuffle.  IGNORED: inward, use_poly_solver, num_lo_steps,
+ * num_lsq_iterations (estimate_pairwise_five_point sets both 0), non_min_sample_multiplier, min_sample_multiplicator,
+ * final_least_squares and mode (reference-trace only; there is no fixed-budget form).
+ *
+ * The control flow is RansacLib's for a minimal sample of five, draw for draw (n = 5..7 take ShuffleSample, n >= 8 DrawSample; fewer than
+ * five correspondences: no model).  SteweniusEstimator::NonMinimalSolver returns 0 and LeastSquares is empty, so LocalOptimization and the
+ * final least squares change no model: LocalOptimization still runs where the reference runs it (it counts in stats and its shuffle of the
+ * relaxed inlier list advances the second random stream), the final least squares -- a re-score of the same model -- is not run.
+ *
+ * Departures from the reference, all stated here:
+ *  * The minimal solver is written from the mathematics (nullspace, the ten cubic constraints, elimination to a degree-10 polynomial in
+ *    one coordinate, real roots by bracketing), not from the reference's generated code, and returns the REAL solutions only, in ascending
+ *    order of that coordinate.  The reference also returns the real parts of complex eigenvectors (stewenius_estimator.cpp:40-57), which
+ *    satisfy no constraint; they can only win an iteration's score by accident.  A sample whose 5x9 system is rank-deficient (a row's part
+ *    outside the others below 1e-10 of its length) or whose elimination meets a pivot below 1e-12 yields no model.
+ *  * Agreement with a build of the reference's solver_stewenius is not pinned (it needs Eigen); tests compare with a numpy restatement.
+ *  * num_inliers counts the inlier flags (the existing call's convention); RansacLib's returned count is that of the same model.
+ *  * With two equal singular values, which rotation DecomposeEssentialMatrix calls R1 and the sign of t are the SVD routine's choice.  Here
+ *    the entry of t of largest magnitude is made positive and R1 is the rotation with <[t]x R1, E> > 0; the four candidates are then
+ *    (R1, t) (R2, t) (R1, -t) (R2, -t) and the last one with the largest vote wins, as in the reference.  The order matters only in a tie. */
+int ssfm_ransac5_batch(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pair_ptr, const double* u, const double* v,
+                       double squared_inlier_threshold, const ssfm_ransac_options* o, double* E, double* R, double* t,
+                       uint8_t* inlier_mask, int32_t* num_inliers, double* scores, uint32_t* stats);
+/* The same from feature tables and match lists: the arguments of ssfm_ransac_batch_indexed plus t. */
+int ssfm_ransac5_batch_indexed(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, const double* feat_rays,
+                               int32_t num_pairs, const int32_t* pair_frame0, const int32_t* pair_frame1, const int32_t* match_ptr,
+                               const int32_t* match_idx0, const int32_t* match_idx1,
+                               double squared_inlier_threshold, const ssfm_ransac_options* o, double* E, double* R, double* t,
+                               uint8_t* inlier_mask, int32_t* num_inliers, double* scores, uint32_t* stats);
+/* Probes of the pieces; each runs the device function the batch kernel runs.
+ * ssfm_fivepoint_solver_probe: the minimal solver on S samples (samples [S*5] ray indices) -> Es [S*10*9] (column-major 3x3, zero beyond
+ *   counts[s]), counts [S].
+ * ssfm_fivepoint_residual_probe: the residual of T models (Es [T*9]) on every ray -> errors [T*n].
+ * ssfm_fivepoint_pose_probe: PoseFromEssentialMatrix of task k on the rays lists[task_ptr[k] .. task_ptr[k+1]) with E [tasks*9] ->
+ *   R [tasks*9], t [tasks*3], votes [tasks*4] (the four candidates in the order above).
+ * ssfm_fivepoint_max_lds_rays: the largest pair whose rays the batch kernel keeps in LDS (5 doubles per ray beside the generator states);
+ *   larger pairs, or every pair while SSFM_RANSAC5_FORCE_GLOBAL=1 is set (read at call time), read their rays from global memory. */
+int ssfm_fivepoint_solver_probe(ssfm_ctx* ctx, int32_t n, const double* u, const double* v, int32_t S, const int32_t* samples, double* Es, int32_t* counts);
+int ssfm_fivepoint_residual_probe(ssfm_ctx* ctx, int32_t n, const double* u, const double* v, int32_t T, const double* Es, double* errors);
+int ssfm_fivepoint_pose_probe(ssfm_ctx* ctx, int32_t n, const double* u, const double* v, int32_t tasks, const int32_t* task_ptr,
+                              const int32_t* lists, const double* E, double* R, double* t, int32_t* votes);
+int32_t ssfm_fivepoint_max_lds_rays(void);
 /* ---- brute-force descriptor matching: match() / match_exhaustive() (examples/spherical_sfm_tools.cpp:235-251, :575-600) ---------------
  * Per pair, train = the descriptors of frame pair_frame0[p] (n0 x dim floats), query = those of pair_frame1[p] (n1 x dim).  For every query i:
  * its nearest train j1 and second nearest j2 by L2 distance (cv::BFMatcher::knnMatch(query, train, 2)), dist = sqrtf(sum (q - t)^2) as a float;

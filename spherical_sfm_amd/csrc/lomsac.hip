@@ -35,16 +35,6 @@ struct LoOpts {
     int num_lo_steps, num_lsq_it, min_sample_mult, non_min_mult, final_lsq, inward, min_num_inliers, fast_shuffle;
 };
 
-__device__ __forceinline__ unsigned num_required_iterations(double ratio, double pmiss, int ssize, unsigned mn, unsigned mx) {   // utils.h:110-140
-    if (ratio <= 0.0) return mx;
-    if (ratio >= 1.0) return mn;
-    const double pn = 1.0 - pow(ratio, (double)ssize);
-    if (pn >= 0.99999999999999) return mx;
-    const double it = ceil(log(pmiss) / log(pn) + 0.5);
-    const unsigned r = (it >= 4294967295.0) ? 4294967295u : (unsigned)it;
-    return max(mn, min(r, mx));
-}
-
 // SphericalEstimator::NonMinimalSolver (src/spherical_estimator.cpp:86-108): the action-matrix solver on 4..9 rays, the candidate with
 // the least Sampson sum over the sample wins (first of equals).  One thread runs it.
 __device__ int nonminimal_solver_dev(const int* sample, int ns, const double* pu, const double* pv, double* Eout) {

@@ -215,6 +215,10 @@ int lomsac_launch(ssfm_ctx* ctx, hipStream_t st, int num_pairs, int max_n, const
                   const ssfm_ransac_options& O, double sq_thresh, const unsigned* d_mt_seeded, int* d_lists, double* d_E, double* d_score, double* d_R,
                   unsigned char* d_mask, int* d_nin, unsigned* d_stats);
 bool lomsac_needs_global_lists(int max_n);
+// fivepoint.hip: the same slab through k_lomsac5_trace (five-point estimator; keeps no inlier lists, writes t beside R)
+int lomsac5_launch(ssfm_ctx* ctx, hipStream_t st, int num_pairs, int max_n, const int* d_pair_ptr, const double* d_u, const double* d_v,
+                   const ssfm_ransac_options& O, double sq_thresh, const unsigned* d_mt_seeded, double* d_E, double* d_score, double* d_R, double* d_t,
+                   unsigned char* d_mask, int* d_nin, unsigned* d_stats);
 }
 
 // Pairs are streamed through the GPU in slabs (BASELINE configs[3]: 2000 frames = 2.0 M pairs x 500 correspondences = 48 GB of rays, more
@@ -239,13 +243,15 @@ k_gather_rays(const int* __restrict__ ptr, const int* __restrict__ off01, const 
 
 static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pair_ptr, const double* u, const double* v, double sq_thresh,
                              const ssfm_ransac_options& O, const int32_t* pair_id, double* E_out, double* R_out, uint8_t* inlier_mask,
-                             int32_t* num_inliers, double* scores, uint32_t* stats_out, const RansacIndexed* X = nullptr) {
+                             int32_t* num_inliers, double* scores, uint32_t* stats_out, const RansacIndexed* X = nullptr,
+                             bool five = false /* the five-point estimator (trace mode) */, double* t_out = nullptr /* five: [pairs*3] */,
+                             const char* who = "ssfm_ransac_batch" /* the entry point, for its error messages */) {
     SSFM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (O.mode != SSFM_RANSAC_FIXED_BUDGET && O.mode != SSFM_RANSAC_REFERENCE_TRACE) return fail(ctx, SSFM_ERR_INVALID, "ssfm_ransac_batch: unknown mode");
+    if (O.mode != SSFM_RANSAC_FIXED_BUDGET && O.mode != SSFM_RANSAC_REFERENCE_TRACE) return fail(ctx, SSFM_ERR_INVALID, std::string(who) + ": unknown mode");
     if (O.mode == SSFM_RANSAC_REFERENCE_TRACE && (O.min_sample_multiplicator < 1 || O.min_sample_multiplicator > 21 || O.non_min_sample_multiplier < 1 || O.non_min_sample_multiplier > 3 ||
                                                   O.num_lo_steps < 0 || O.num_lsq_iterations < 0 || !(O.success_probability > 0.0 && O.success_probability < 1.0)))
-        return fail(ctx, SSFM_ERR_INVALID, "ssfm_ransac_batch: LO-RANSAC options out of range (min_sample_multiplicator 1..21, non_min_sample_multiplier 1..3)");
-    for (int p = 0; p < num_pairs; p++) if (pair_ptr[p + 1] < pair_ptr[p]) return fail(ctx, SSFM_ERR_INVALID, "ssfm_ransac_batch: pair_ptr must ascend");
+        return fail(ctx, SSFM_ERR_INVALID, std::string(who) + ": LO-RANSAC options out of range (min_sample_multiplicator 1..21, non_min_sample_multiplier 1..3)");
+    for (int p = 0; p < num_pairs; p++) if (pair_ptr[p + 1] < pair_ptr[p]) return fail(ctx, SSFM_ERR_INVALID, std::string(who) + ": pair_ptr must ascend");
     const bool trace = O.mode == SSFM_RANSAC_REFERENCE_TRACE;
     int max_n = 0; for (int p = 0; p < num_pairs; p++) max_n = std::max(max_n, pair_ptr[p + 1] - pair_ptr[p]);
     const size_t lds_fixed = (size_t)6 * max_n * sizeof(double);
@@ -268,11 +274,11 @@ static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pa
     hipEvent_t kt0[2] = {nullptr, nullptr}, kt1[2] = {nullptr, nullptr};      // around the kernels of a slab: ssfm_ransac_last_kernel_ms (bench.py: FP64 rate of the scoring)
     ctx->ransac_kernel_ms = 0.0;
     // per-slab device buffers x 2 (upload of the next slab overlaps the kernels of this one); pinned staging x 2
-    struct Slot { DevBuf<int> ptr, pid, nin, lists, idx, off; DevBuf<double> u, v, E, S, R; DevBuf<unsigned char> mask; DevBuf<unsigned> stats;
+    struct Slot { DevBuf<int> ptr, pid, nin, lists, idx, off; DevBuf<double> u, v, E, S, R, T; DevBuf<unsigned char> mask; DevBuf<unsigned> stats;
                   double* h_uv = nullptr; int* h_ptr = nullptr; int* h_idx = nullptr; double* h_res = nullptr; unsigned char* h_mask = nullptr; int* h_nin = nullptr; unsigned* h_stats = nullptr; } slot[2];
     DevBuf<unsigned> dmt; DevBuf<double> frays;
     const int nslot = ns > 1 ? 2 : 1;
-    const bool glists = trace ? lomsac_needs_global_lists(max_n) : true;
+    const bool glists = five ? false : (trace ? lomsac_needs_global_lists(max_n) : true);
     int rc = SSFM_OK;
     auto body = [&]() -> int {
         if (trace) { std::vector<unsigned> seeded(624); mt_seed_host(O.seed, seeded.data()); SSFM_HIP_CHECK(ctx, upload(dmt, seeded, st)); }
@@ -294,12 +300,13 @@ static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pa
             SSFM_HIP_CHECK(ctx, s.S.alloc(cap_pairs)); SSFM_HIP_CHECK(ctx, s.R.alloc((size_t)9 * cap_pairs)); SSFM_HIP_CHECK(ctx, s.mask.alloc(cap_rays));
             SSFM_HIP_CHECK(ctx, s.stats.alloc((size_t)2 * cap_pairs));
             if (glists) SSFM_HIP_CHECK(ctx, s.lists.alloc((trace ? 2 : 1) * cap_rays));
+            if (five) SSFM_HIP_CHECK(ctx, s.T.alloc((size_t)3 * cap_pairs));
             if (dev) {}                                       // (the hooks own the per-slot list buffers)
             else if (X) { SSFM_HIP_CHECK(ctx, s.idx.alloc(2 * cap_rays)); SSFM_HIP_CHECK(ctx, s.off.alloc((size_t)2 * cap_pairs));
                      SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_idx, (2 * cap_rays + (size_t)2 * cap_pairs) * sizeof(int), hipHostMallocDefault)); }
             else SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_uv, 6 * cap_rays * sizeof(double), hipHostMallocDefault));
             SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_ptr, (size_t)(2 * cap_pairs + 1) * sizeof(int), hipHostMallocDefault));
-            SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_res, (size_t)19 * cap_pairs * sizeof(double), hipHostMallocDefault));
+            SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_res, (size_t)(five ? 22 : 19) * cap_pairs * sizeof(double), hipHostMallocDefault));
             if (!dev) SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_mask, cap_rays, hipHostMallocDefault));
             SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_nin, (size_t)cap_pairs * sizeof(int), hipHostMallocDefault));
             SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_stats, (size_t)2 * cap_pairs * sizeof(unsigned), hipHostMallocDefault));
@@ -370,6 +377,7 @@ static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pa
                 if (E_out) rm_to_cm(s.h_res + 9 * (size_t)i, E_out + 9 * (size_t)(p0 + i));
                 if (R_out) rm_to_cm(s.h_res + 9 * (size_t)cap_pairs + 9 * (size_t)i, R_out + 9 * (size_t)(p0 + i));
                 if (scores) scores[p0 + i] = s.h_res[18 * (size_t)cap_pairs + i];
+                if (five && t_out) for (int k = 0; k < 3; k++) t_out[3 * (size_t)(p0 + i) + k] = s.h_res[19 * (size_t)cap_pairs + 3 * (size_t)i + k];
                 if (num_inliers) num_inliers[p0 + i] = s.h_nin[i];
                 if (stats_out) { stats_out[2 * (size_t)(p0 + i)] = s.h_stats[2 * i]; stats_out[2 * (size_t)(p0 + i) + 1] = s.h_stats[2 * i + 1]; }
             }
@@ -385,7 +393,10 @@ static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pa
             SSFM_HIP_CHECK(ctx, hipEventRecord(kt0[k % nslot], st));
             if (dev) { const int r = dev->gather(st, k % nslot, np, s.ptr.p, s.u.p, s.v.p); if (r) return r; }
             else if (X && np > 0) hipLaunchKernelGGL(k_gather_rays, dim3(np), dim3(256), 0, st, s.ptr.p, s.off.p, s.idx.p, s.idx.p + cap_rays, frays.p, s.u.p, s.v.p);
-            if (trace) {
+            if (five) {
+                const int r = lomsac5_launch(ctx, st, np, slab_max_n, s.ptr.p, s.u.p, s.v.p, O, sq_thresh, dmt.p, s.E.p, s.S.p, s.R.p, s.T.p, s.mask.p, s.nin.p, s.stats.p);
+                if (r) return r;
+            } else if (trace) {
                 const int r = lomsac_launch(ctx, st, np, slab_max_n, s.ptr.p, s.u.p, s.v.p, (int)nr, O, sq_thresh, dmt.p, glists ? s.lists.p : nullptr, s.E.p, s.S.p, s.R.p, s.mask.p, s.nin.p, s.stats.p);
                 if (r) return r;
             } else {
@@ -408,6 +419,7 @@ static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pa
                 SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_res + 9 * (size_t)cap_pairs, s.R.p, (size_t)9 * np * sizeof(double), hipMemcpyDeviceToHost, st));
                 SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_res + 18 * (size_t)cap_pairs, s.S.p, (size_t)np * sizeof(double), hipMemcpyDeviceToHost, st));
                 if (nr) SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_mask, s.mask.p, nr, hipMemcpyDeviceToHost, st));
+                if (five) SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_res + 19 * (size_t)cap_pairs, s.T.p, (size_t)3 * np * sizeof(double), hipMemcpyDeviceToHost, st));
             }
             SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_nin, s.nin.p, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, st));
             SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_stats, s.stats.p, (size_t)2 * np * sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -421,7 +433,7 @@ static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pa
     if (rc != SSFM_OK) { (void)hipStreamSynchronize(st); if (cs) (void)hipStreamSynchronize(cs); }
     for (int b = 0; b < 2; b++) {
         Slot& s = slot[b];
-        s.ptr.free(); s.pid.free(); s.nin.free(); s.lists.free(); s.u.free(); s.v.free(); s.E.free(); s.S.free(); s.R.free(); s.mask.free(); s.stats.free();
+        s.ptr.free(); s.pid.free(); s.nin.free(); s.lists.free(); s.u.free(); s.v.free(); s.E.free(); s.S.free(); s.R.free(); s.T.free(); s.mask.free(); s.stats.free();
         s.idx.free(); s.off.free(); if (s.h_idx) (void)hipHostFree(s.h_idx);
         if (s.h_uv) (void)hipHostFree(s.h_uv); if (s.h_ptr) (void)hipHostFree(s.h_ptr); if (s.h_res) (void)hipHostFree(s.h_res);
         if (s.h_mask) (void)hipHostFree(s.h_mask); if (s.h_nin) (void)hipHostFree(s.h_nin); if (s.h_stats) (void)hipHostFree(s.h_stats);
@@ -469,6 +481,44 @@ extern "C" int ssfm_ransac_batch(ssfm_ctx* ctx, int32_t num_pairs, const int32_t
     if (!ctx || !pair_ptr || !u || !v || num_pairs <= 0) return fail(ctx, SSFM_ERR_INVALID, "ssfm_ransac_batch: bad arguments");
     ssfm_ransac_options O; if (opt) O = *opt; else ssfm_ransac_default_options(&O);
     return ransac_batch_impl(ctx, num_pairs, pair_ptr, u, v, sq_thresh, O, nullptr, E_out, R_out, inlier_mask, num_inliers, scores, stats);
+}
+
+// ---- general relative pose: the five-point estimator through the same slabs (fivepoint.hip) ----------------------------------------
+// trace mode only; the fields of the options that the five-point path has no use for are ignored (include/ssfm.h)
+static ssfm_ransac_options ransac5_options(const ssfm_ransac_options* opt) {
+    ssfm_ransac_options D; ssfm_ransac_default_options(&D);
+    if (!opt) return D;
+    ssfm_ransac_options O = *opt;
+    O.mode = SSFM_RANSAC_REFERENCE_TRACE; O.inward = D.inward; O.use_poly_solver = D.use_poly_solver; O.num_lo_steps = D.num_lo_steps;
+    O.num_lsq_iterations = D.num_lsq_iterations; O.non_min_sample_multiplier = D.non_min_sample_multiplier;
+    if (O.min_sample_multiplicator < 1 || O.min_sample_multiplicator > 21) O.min_sample_multiplicator = D.min_sample_multiplicator;      // (sizes a list nobody reads here)
+    return O;
+}
+extern "C" int ssfm_ransac5_batch(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pair_ptr, const double* u, const double* v, double sq_thresh,
+                                  const ssfm_ransac_options* opt, double* E_out, double* R_out, double* t_out, uint8_t* inlier_mask, int32_t* num_inliers,
+                                  double* scores, uint32_t* stats) {
+    // the shape of the request is checked before the context, so that a caller without a device still learns what is wrong with it
+    if (num_pairs <= 0 || !pair_ptr) return fail(ctx, SSFM_ERR_INVALID, "ssfm_ransac5_batch: num_pairs must be positive and pair_ptr given");
+    for (int p = 0; p < num_pairs; p++) if (pair_ptr[p + 1] < pair_ptr[p] || pair_ptr[p] < 0) return fail(ctx, SSFM_ERR_INVALID, "ssfm_ransac5_batch: pair_ptr must ascend from a non-negative start");
+    if (!ctx || !u || !v) return fail(ctx, SSFM_ERR_INVALID, "ssfm_ransac5_batch: ctx, u and v must not be NULL");
+    const ssfm_ransac_options O = ransac5_options(opt);
+    return ransac_batch_impl(ctx, num_pairs, pair_ptr, u, v, sq_thresh, O, nullptr, E_out, R_out, inlier_mask, num_inliers, scores, stats, nullptr, true, t_out, "ssfm_ransac5_batch");
+}
+extern "C" int ssfm_ransac5_batch_indexed(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, const double* feat_rays, int32_t num_pairs,
+                                          const int32_t* pair_frame0, const int32_t* pair_frame1, const int32_t* match_ptr, const int32_t* match_idx0,
+                                          const int32_t* match_idx1, double sq_thresh, const ssfm_ransac_options* opt, double* E_out, double* R_out, double* t_out,
+                                          uint8_t* inlier_mask, int32_t* num_inliers, double* scores, uint32_t* stats) {
+    if (num_frames <= 0 || num_pairs <= 0) return fail(ctx, SSFM_ERR_INVALID, "ssfm_ransac5_batch_indexed: num_frames and num_pairs must be positive");
+    if (!ctx || !feat_ptr || !feat_rays || !pair_frame0 || !pair_frame1 || !match_ptr || !match_idx0 || !match_idx1)
+        return fail(ctx, SSFM_ERR_INVALID, "ssfm_ransac5_batch_indexed: ctx and the arrays must not be NULL");
+    for (int f = 0; f < num_frames; f++) if (feat_ptr[f + 1] < feat_ptr[f]) return fail(ctx, SSFM_ERR_INVALID, "ssfm_ransac5_batch_indexed: feat_ptr must ascend");
+    for (int p = 0; p < num_pairs; p++) {
+        const int f0 = pair_frame0[p], f1 = pair_frame1[p];
+        if (f0 < 0 || f0 >= num_frames || f1 < 0 || f1 >= num_frames || match_ptr[p + 1] < match_ptr[p]) return fail(ctx, SSFM_ERR_INVALID, "ssfm_ransac5_batch_indexed: frame index out of range or match_ptr not ascending");
+    }
+    const ssfm_ransac_options O = ransac5_options(opt);
+    const RansacIndexed X{num_frames, feat_ptr, feat_rays, pair_frame0, pair_frame1, match_idx0, match_idx1};
+    return ransac_batch_impl(ctx, num_pairs, match_ptr, nullptr, nullptr, sq_thresh, O, nullptr, E_out, R_out, inlier_mask, num_inliers, scores, stats, &X, true, t_out, "ssfm_ransac5_batch_indexed");
 }
 
 // Every rank enters with the results of ITS pairs (ids = their global indices, lptr = their local CSR) and leaves with all of them: one sum

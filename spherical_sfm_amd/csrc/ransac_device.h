@@ -404,6 +404,16 @@ __device__ void decompose_E_dev(const double* E, bool inward, double* r) {      
 }
 
 
+__device__ __forceinline__ unsigned num_required_iterations(double ratio, double pmiss, int ssize, unsigned mn, unsigned mx) {   // utils.h:110-140
+    if (ratio <= 0.0) return mx;
+    if (ratio >= 1.0) return mn;
+    const double pn = 1.0 - pow(ratio, (double)ssize);
+    if (pn >= 0.99999999999999) return mx;
+    const double it = ceil(log(pmiss) / log(pn) + 0.5);
+    const unsigned r = (it >= 4294967295.0) ? 4294967295u : (unsigned)it;
+    return max(mn, min(r, mx));
+}
+
 // ---- workgroup-cooperative pieces (every thread of the block calls them with the same arguments: uniform control flow) -----------
 
 // GetInliers (include/RansacLib/ransac.h:311-336): indices i with Sampson(E, i) < thresh, ascending, into list; returns the count.

@@ -2,7 +2,8 @@
 //   match_exhaustive + estimate_pairwise   against   estimate_pairwise_from_features
 //   demo_match <dir with keyframes.txt, features.dat> <focal> <cx> <cy> <inlier threshold px> <min inliers>
 // Writes <dir>/match_exhaustive.txt (one line per pair: index0 index1 n, then n x "j i") and <dir>/match_ratio.txt (match() of the first two keyframes with
-// ratio 1.5, same format) for the test to compare with its own matcher; prints DEMO_MATCH_RESULT.
+// ratio 1.5, same format) for the test to compare with its own matcher; prints DEMO_MATCH_RESULT.  Then estimate_pairwise_five_point on the same lists:
+// <dir>/five_point.txt (one line per accepted pair: index0 index1 n, n x "j i", the nine entries of R column-major as %.17g) and DEMO_FIVEPOINT_RESULT.
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -38,5 +39,17 @@ int main(int argc, char** argv) {
     for (size_t k = 0; equal && k < a.size(); k++) equal = a[k].index0 == b[k].index0 && a[k].index1 == b[k].index1 && a[k].matches == b[k].matches && a[k].R == b[k].R;
     std::printf("DEMO_MATCH_RESULT keyframes=%zu pairs=%zu match_same=%d accepted_a=%zu accepted_b=%zu loops_a=%d loops_b=%d equal=%d\n", keyframes.size(), all.size(),
                 match_same, a.size(), b.size(), loops_a, loops_b, equal);
+    std::vector<ImageMatch> five;
+    const int loops5 = estimate_pairwise_five_point(sfm.GetContext(), intrinsics, keyframes, all, thresh, min_inliers, five);
+    if (FILE* f = std::fopen((dir + "/five_point.txt").c_str(), "w")) {
+        for (const ImageMatch& m : five) {
+            std::fprintf(f, "%d %d %zu", m.index0, m.index1, m.matches.size());
+            for (auto& kv : m.matches) std::fprintf(f, " %zu %zu", kv.first, kv.second);
+            for (int q = 0; q < 9; q++) std::fprintf(f, " %.17g", m.R[q]);
+            std::fprintf(f, "\n");
+        }
+        std::fclose(f);
+    }
+    std::printf("DEMO_FIVEPOINT_RESULT accepted=%zu loops=%d\n", five.size(), loops5);
     return 0;
 }

@@ -7,8 +7,10 @@
 // find_largest_connected_component (:96-122).
 // -viewgraph: the frames need not be in capture order -- the focal search chains its trial rotations along a breadth-first spanning tree of the matches
 // (find_best_focal_length_random with sequential = false -> ssfm_focal_search_graph) instead of along the matches (k-1, k).  Without it nothing changes.
+// -fivepoint: the pairwise stage is general relative pose (estimate_pairwise_five_point, examples/run_spherical_sfm_uncalib.cpp:107-110) instead of the spherical
+// three-point estimator: with -match on the lists of match_exhaustive, without it on the matches of matches.dat, whose rotations it replaces.
 //   run_spherical_sfm_uncalib -output <dir with keyframes.txt, features.dat, matches.dat> -width W -height H [-generalba] [-inward]
-//                             [-match [-inlierthresh T] [-mininliers N]] [-viewgraph]
+//                             [-match] [-fivepoint] [-inlierthresh T] [-mininliers N] [-viewgraph]
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -16,7 +18,7 @@
 using namespace sphericalsfm;
 
 int main(int argc, char** argv) {
-    std::string output; bool inward = false, generalba = false, match_mode = false, viewgraph = false; int width = 0, height = 0, num_trials = 1024, mininliers = 100; unsigned seed = 0; double inlierthresh = 2.0;
+    std::string output; bool inward = false, generalba = false, match_mode = false, viewgraph = false, fivepoint = false; int width = 0, height = 0, num_trials = 1024, mininliers = 100; unsigned seed = 0; double inlierthresh = 2.0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "-output" && i + 1 < argc) output = argv[++i];
@@ -27,6 +29,7 @@ int main(int argc, char** argv) {
         else if (a == "-inward") inward = true;
         else if (a == "-generalba") generalba = true;
         else if (a == "-match") match_mode = true;
+        else if (a == "-fivepoint") fivepoint = true;
         else if (a == "-inlierthresh" && i + 1 < argc) inlierthresh = std::atof(argv[++i]);
         else if (a == "-mininliers" && i + 1 < argc) mininliers = std::atoi(argv[++i]);
         else if (a == "-sequential") viewgraph = false;
@@ -42,7 +45,15 @@ int main(int argc, char** argv) {
 
     SfM sfm_probe(Intrinsics(focal_guess, centerx, centery));                                       // owns the library context for the pairwise stage and the search
     int loop_closures = -1;
-    if (match_mode) {                                                                               // :96-122
+    if (fivepoint) {                                                                                // :107-110
+        std::vector<ImageMatch> all;
+        if (match_mode) match_exhaustive(sfm_probe.GetContext(), keyframes, all); else all.swap(image_matches);
+        image_matches.clear();
+        loop_closures = estimate_pairwise_five_point(sfm_probe.GetContext(), Intrinsics(focal_guess, centerx, centery), keyframes, all, inlierthresh, mininliers, image_matches);
+        if (loop_closures == 0) { std::cout << "error: no loop closures found\n"; return 1; }
+        find_largest_connected_component(keyframes, image_matches);
+        if (image_matches.empty()) { std::cout << "error: no matches found\n"; return 1; }
+    } else if (match_mode) {                                                                        // :96-122
         loop_closures = estimate_pairwise_from_features(sfm_probe.GetContext(), Intrinsics(focal_guess, centerx, centery), keyframes, inlierthresh, mininliers, inward, image_matches);
         if (loop_closures == 0) { std::cout << "error: no loop closures found\n"; return 1; }
         find_largest_connected_component(keyframes, image_matches);

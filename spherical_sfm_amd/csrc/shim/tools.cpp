@@ -63,6 +63,55 @@ int estimate_pairwise(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::ve
     return loop_closure_count;
 }
 
+int estimate_pairwise_five_point(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, const std::vector<ImageMatch>& image_matches,
+                      double inlier_threshold, int min_num_inliers, std::vector<ImageMatch>& image_matches_out) {
+    const double kinv = 1.0 / intrinsics.focal;                                           // Kinv(0,0)
+    const double sq_thresh = inlier_threshold * inlier_threshold * kinv * kinv;           // :440
+    // the reference enumerates all (index0 < index1) and takes the FIRST stored match set of each pair
+    std::map<std::pair<int, int>, const ImageMatch*> first;
+    for (const ImageMatch& m : image_matches) if (m.index0 < m.index1) first.emplace(std::make_pair(m.index0, m.index1), &m);
+    std::vector<const ImageMatch*> cand;
+    for (auto& kv : first) if ((int)kv.second->matches.size() >= min_num_inliers && !kv.second->matches.empty()) cand.push_back(kv.second);   // :476
+    if (cand.empty()) return 0;
+    // per-frame feature rays Kinv * (x, y, 1) (:484-500, once per feature) + per-pair match lists: ssfm_ransac5_batch_indexed gathers the ray pairs on the device
+    const int nf = (int)keyframes.size();
+    std::vector<int32_t> feat_ptr(nf + 1, 0);
+    for (int f = 0; f < nf; f++) feat_ptr[f + 1] = feat_ptr[f] + (int32_t)keyframes[f].features.points.size();
+    std::vector<double> rays((size_t)3 * std::max(1, (int)feat_ptr[nf]));
+    for (int f = 0; f < nf; f++) {
+        const Features& ft = keyframes[f].features;
+        for (size_t k = 0; k < ft.points.size(); k++) {
+            double* r = &rays[3 * ((size_t)feat_ptr[f] + k)];
+            r[0] = (ft.points[k].x - intrinsics.centerx) * kinv; r[1] = (ft.points[k].y - intrinsics.centery) * kinv; r[2] = 1.0;
+        }
+    }
+    std::vector<int32_t> pair_ptr(1, 0), pf0, pf1, m0, m1;
+    for (const ImageMatch* m : cand) {
+        pf0.push_back(m->index0); pf1.push_back(m->index1);
+        for (auto& kv : m->matches) { m0.push_back((int32_t)kv.first); m1.push_back((int32_t)kv.second); }
+        pair_ptr.push_back((int32_t)m0.size());
+    }
+    ssfm_ransac_options O; ssfm_ransac_default_options(&O);
+    O.min_num_inliers = min_num_inliers;                                                  // :441-445 (the LO options it sets have no effect on this estimator)
+    const int P = (int)cand.size();
+    std::vector<double> R((size_t)9 * P); std::vector<uint8_t> mask(std::max<size_t>(1, m0.size())); std::vector<int32_t> nin(P);
+    if (ssfm_ransac5_batch_indexed(ctx, nf, feat_ptr.data(), rays.data(), P, pf0.data(), pf1.data(), pair_ptr.data(), m0.data(), m1.data(), sq_thresh, &O, nullptr, R.data(), nullptr,
+                                   mask.data(), nin.data(), nullptr, nullptr) != SSFM_OK) {
+        std::cout << "error: " << ssfm_last_error(ctx) << "\n"; std::exit(1);
+    }
+    int loop_closure_count = 0;
+    for (int k = 0; k < P; k++) {
+        if (!(nin[k] > min_num_inliers)) continue;                                        // :535
+        Matches inl; size_t j = (size_t)pair_ptr[k];
+        for (auto& kv : cand[k]->matches) { if (mask[j++]) inl[kv.first] = kv.second; }
+        if (inl.empty()) continue;
+        Mat3 Rk; for (int q = 0; q < 9; q++) Rk[q] = R[9 * (size_t)k + q];
+        if (cand[k]->index0 + 1 != cand[k]->index1) loop_closure_count++;
+        image_matches_out.push_back(ImageMatch(cand[k]->index0, cand[k]->index1, inl, Rk));
+    }
+    return loop_closure_count;
+}
+
 // per-frame tables of the C ABI: feat_ptr, descriptors (128 floats per feature), optionally the rays Kinv (x, y, 1)
 static void feature_tables(const std::vector<const Features*>& fs, const Intrinsics* intrinsics, std::vector<int32_t>& feat_ptr, std::vector<float>& descs, std::vector<double>* rays) {
     const int nf = (int)fs.size();

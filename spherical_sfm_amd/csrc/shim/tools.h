@@ -49,6 +49,13 @@ bool read_feature_tracks(const std::string& outputpath, std::vector<Keyframe>& k
 int estimate_pairwise(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, const std::vector<ImageMatch>& image_matches,
                       double inlier_threshold, int min_num_inliers, bool inward, std::vector<ImageMatch>& image_matches_out);
 
+// estimate_pairwise_five_point (spherical_sfm_tools.cpp:433-573, the `-fivepoint` branch of run_spherical_sfm_uncalib): the same candidate rule (the first
+// stored match set of every pair index0 < index1; `m01.size() < min_num_inliers` skips) and the same output order as estimate_pairwise, but general relative pose --
+// LO-MSAC over the five-point estimator and PoseFromEssentialMatrix on the inliers -- through ssfm_ransac5_batch_indexed.  No `inward`: nothing ties t to R.
+// Single GPU (the sharded forms have no five-point counterpart).  Returns the loop-closure count.
+int estimate_pairwise_five_point(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, const std::vector<ImageMatch>& image_matches,
+                                 double inlier_threshold, int min_num_inliers, std::vector<ImageMatch>& image_matches_out);
+
 // match (spherical_sfm_tools.cpp:235-251) and match_exhaustive (:575-600) over ssfm_match_pairs: features0 is the train set, features1 the query set, m01 maps a
 // feature of features0 to the LAST query that chose it; match_exhaustive appends one ImageMatch per pair index0 < index1 -- every pair, also one without a match,
 // as the reference does -- where index0 / index1 are the POSITIONS in `keyframes` (the reference's loop counters; what estimate_pairwise,

@@ -68,6 +68,81 @@ def estimate_indexed(ctx, feat_ptr, feat_rays, pair_frame0, pair_frame1, match_p
     return dict(E=_unflat(E), R=_unflat(R), mask=mask[:int(mp[-1])], num_inliers=nin, scores=sc, iterations=st[0::2].copy(), lo_runs=st[1::2].copy())
 
 
+def ransac5_batch(ctx, pair_ptr, U, V, squared_inlier_threshold, options=None, **kw):
+    """ssfm_ransac5_batch: general relative pose (five-point LO-MSAC) on CSR-style arrays, pair p owns rays [pair_ptr[p], pair_ptr[p+1]) of U, V.
+    -> dict(E, R (P,3,3), t (P,3), mask, num_inliers, scores, iterations, lo_runs); R = identity, t = 0 where a pair is not accepted."""
+    ptr = np.ascontiguousarray(pair_ptr, np.int32); U = np.ascontiguousarray(U, np.float64).reshape(-1, 3); V = np.ascontiguousarray(V, np.float64).reshape(-1, 3)
+    if len(U) == 0:
+        U = np.zeros((1, 3)); V = np.zeros((1, 3))
+    o = options or default_options(**kw)
+    P = len(ptr) - 1
+    E = np.zeros(9 * P); R = np.zeros(9 * P); t = np.zeros(3 * P); mask = np.zeros(max(int(ptr[-1]), 1), np.uint8); nin = np.zeros(P, np.int32); sc = np.zeros(P)
+    st = np.zeros(2 * P, np.uint32)
+    _lib.check(_lib.lib().ssfm_ransac5_batch(ctx._p, P, ptr.ctypes.data_as(c_i32_p), U.ctypes.data_as(c_double_p), V.ctypes.data_as(c_double_p),
+                                             squared_inlier_threshold, C.byref(o), E.ctypes.data_as(c_double_p), R.ctypes.data_as(c_double_p),
+                                             t.ctypes.data_as(c_double_p), mask.ctypes.data_as(c_u8_p), nin.ctypes.data_as(c_i32_p),
+                                             sc.ctypes.data_as(c_double_p), st.ctypes.data_as(c_u32_p)), ctx._p)
+    return dict(E=_unflat(E), R=_unflat(R), t=t.reshape(P, 3), mask=mask[:int(ptr[-1])], num_inliers=nin, scores=sc, iterations=st[0::2].copy(), lo_runs=st[1::2].copy())
+
+
+def ransac5_batch_indexed(ctx, feat_ptr, feat_rays, pair_frame0, pair_frame1, match_ptr, match_idx0, match_idx1, squared_inlier_threshold, options=None, **kw):
+    """ssfm_ransac5_batch_indexed: the same from per-frame feature rays and per-pair match lists (the arguments of estimate_indexed)."""
+    fp = np.ascontiguousarray(feat_ptr, np.int32); fr = np.ascontiguousarray(feat_rays, np.float64)
+    f0 = np.ascontiguousarray(pair_frame0, np.int32); f1 = np.ascontiguousarray(pair_frame1, np.int32)
+    mp = np.ascontiguousarray(match_ptr, np.int32); m0 = np.ascontiguousarray(match_idx0, np.int32); m1 = np.ascontiguousarray(match_idx1, np.int32)
+    o = options or default_options(**kw)
+    P = len(mp) - 1
+    E = np.zeros(9 * P); R = np.zeros(9 * P); t = np.zeros(3 * P); mask = np.zeros(max(int(mp[-1]), 1), np.uint8); nin = np.zeros(P, np.int32); sc = np.zeros(P)
+    st = np.zeros(2 * P, np.uint32)
+    _lib.check(_lib.lib().ssfm_ransac5_batch_indexed(ctx._p, len(fp) - 1, fp.ctypes.data_as(c_i32_p), fr.ctypes.data_as(c_double_p), P,
+                                                     f0.ctypes.data_as(c_i32_p), f1.ctypes.data_as(c_i32_p), mp.ctypes.data_as(c_i32_p),
+                                                     m0.ctypes.data_as(c_i32_p), m1.ctypes.data_as(c_i32_p), C.c_double(squared_inlier_threshold), C.byref(o),
+                                                     E.ctypes.data_as(c_double_p), R.ctypes.data_as(c_double_p), t.ctypes.data_as(c_double_p),
+                                                     mask.ctypes.data_as(c_u8_p), nin.ctypes.data_as(c_i32_p), sc.ctypes.data_as(c_double_p),
+                                                     st.ctypes.data_as(c_u32_p)), ctx._p)
+    return dict(E=_unflat(E), R=_unflat(R), t=t.reshape(P, 3), mask=mask[:int(mp[-1])], num_inliers=nin, scores=sc, iterations=st[0::2].copy(), lo_runs=st[1::2].copy())
+
+
+def fivepoint_max_lds_rays():
+    """ssfm_fivepoint_max_lds_rays: the largest pair the five-point kernel keeps in LDS (no device needed)"""
+    return int(_lib.lib().ssfm_fivepoint_max_lds_rays())
+
+
+def fivepoint_solver_probe(ctx, u, v, samples):
+    """The five-point minimal solver on given 5-ray samples -> list (per sample) of lists of E (3,3), real solutions only."""
+    u = np.ascontiguousarray(u, np.float64); v = np.ascontiguousarray(v, np.float64); s = np.ascontiguousarray(samples, np.int32).reshape(-1, 5)
+    S = len(s); Es = np.zeros(90 * S); cnt = np.zeros(S, np.int32)
+    _lib.check(_lib.lib().ssfm_fivepoint_solver_probe(ctx._p, len(u), u.ctypes.data_as(c_double_p), v.ctypes.data_as(c_double_p), S,
+                                                      s.ctypes.data_as(c_i32_p), Es.ctypes.data_as(c_double_p), cnt.ctypes.data_as(c_i32_p)), ctx._p)
+    out = []
+    for i in range(S):
+        M = _unflat(Es[90 * i:90 * i + 90])
+        out.append([M[k] for k in range(cnt[i])])
+    return out
+
+
+def fivepoint_residual_probe(ctx, u, v, Es):
+    """FivePointEstimator::EvaluateModelOnPoint of T models on every ray -> (T, n)"""
+    u = np.ascontiguousarray(u, np.float64); v = np.ascontiguousarray(v, np.float64)
+    E = np.ascontiguousarray(np.transpose(np.asarray(Es, np.float64).reshape(-1, 3, 3), (0, 2, 1))).reshape(-1).copy()
+    T = len(E) // 9; err = np.zeros(T * len(u))
+    _lib.check(_lib.lib().ssfm_fivepoint_residual_probe(ctx._p, len(u), u.ctypes.data_as(c_double_p), v.ctypes.data_as(c_double_p), T,
+                                                        E.ctypes.data_as(c_double_p), err.ctypes.data_as(c_double_p)), ctx._p)
+    return err.reshape(T, len(u))
+
+
+def fivepoint_pose_probe(ctx, u, v, lists, Es):
+    """PoseFromEssentialMatrix of task k on the rays lists[k] with Es[k] -> (R (T,3,3), t (T,3), votes (T,4))"""
+    u = np.ascontiguousarray(u, np.float64); v = np.ascontiguousarray(v, np.float64)
+    ptr, flat = _csr(lists); T = len(lists)
+    E = np.ascontiguousarray(np.transpose(np.asarray(Es, np.float64).reshape(-1, 3, 3), (0, 2, 1))).reshape(-1).copy()
+    R = np.zeros(9 * T); t = np.zeros(3 * T); votes = np.zeros(4 * T, np.int32)
+    _lib.check(_lib.lib().ssfm_fivepoint_pose_probe(ctx._p, len(u), u.ctypes.data_as(c_double_p), v.ctypes.data_as(c_double_p), T, ptr.ctypes.data_as(c_i32_p),
+                                                    flat.ctypes.data_as(c_i32_p), E.ctypes.data_as(c_double_p), R.ctypes.data_as(c_double_p),
+                                                    t.ctypes.data_as(c_double_p), votes.ctypes.data_as(c_i32_p)), ctx._p)
+    return _unflat(R), t.reshape(T, 3), votes.reshape(T, 4)
+
+
 def last_kernel_ms(ctx):
     """device time of the kernels of the context's last estimate_* call (ssfm_ransac_last_kernel_ms)"""
     ms = C.c_double(0)

@@ -218,6 +218,34 @@ def make_relative_pose_problem(num_corr=100, *, inward=False, rotation_deg=None,
     return np.ascontiguousarray(u), np.ascontiguousarray(v), R, S @ R, inl
 
 
+def make_general_pose_problem(num_corr=100, *, max_rotation_deg=30.0, focal=1000.0, noise_px=0.0, outlier_frac=0.0, seed=0):
+    """Synthetic pair in GENERAL motion (nothing ties t to R): a random rotation of at most max_rotation_deg about a random axis, a random
+    unit translation, points at depth U(2, 10) in front of camera 0 and in front of camera 1 (x1 = R x0 + t), image-plane noise of noise_px
+    pixels at the given focal length, a fraction of correspondences replaced by uniform outliers.
+    Returns u (n,3), v (n,3) (third component 1), R_gt, t_gt, E_gt = [t]x R, inlier mask."""
+    rng = np.random.default_rng(seed)
+    while True:
+        ax = rng.normal(size=3); ax /= np.linalg.norm(ax)
+        R = so3exp(ax * np.deg2rad(rng.uniform(0.0, max_rotation_deg)))
+        t = rng.normal(size=3); t /= np.linalg.norm(t)
+        u = np.concatenate([rng.uniform(-0.6, 0.6, size=(num_corr, 2)), np.ones((num_corr, 1))], axis=1)
+        X = u * rng.uniform(2.0, 10.0, num_corr)[:, None]
+        P2 = X @ R.T + t
+        if (P2[:, 2] <= 0.1).any():
+            continue
+        v = np.concatenate([P2[:, :2] / P2[:, 2:3], np.ones((num_corr, 1))], axis=1)
+        break
+    sig = noise_px / focal
+    u[:, :2] += sig * rng.normal(size=(num_corr, 2)); v[:, :2] += sig * rng.normal(size=(num_corr, 2))
+    inl = np.ones(num_corr, bool)
+    n_out = int(round(outlier_frac * num_corr))
+    if n_out:
+        idx = rng.choice(num_corr, n_out, replace=False)
+        v[idx, :2] = rng.uniform(-0.8, 0.8, size=(n_out, 2)); inl[idx] = False
+    S = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
+    return np.ascontiguousarray(u), np.ascontiguousarray(v), R, t, S @ R, inl
+
+
 def corrupt_observations(prob, frac=0.1, seed=5, lo=30.0, hi=80.0):
     """Gross outliers for Retriangulate tests: one observation of `frac` of the points is displaced by lo..hi px.
     Returns the ids of the touched points; prob.obs_xy is replaced."""
