@@ -8,6 +8,7 @@
 #include <cstring>
 #include <limits>
 #include <string>
+#include <tuple>
 #include <vector>
 #include "ba_flatten.h"
 #include "ba_kernels.h"
@@ -61,6 +62,18 @@ struct DevBuf {
         if (p) (void)hipFree(p);
         p = nullptr; n = 0; cap_bytes = 0;
     }
+};
+// Frees the buffers it was given, in the order given, when it leaves scope: the temporaries of an entry point, whichever way the entry point
+// returns.  DevBuf itself has no destructor (a handle's buffers are freed by free_all after its stream is synchronised).  The scope does not
+// synchronise: on the path without an error the entry point has done so before the scope ends (ssfm_ctx.h: DevPool's RULE).  On an early return after
+// a failed HIP call the buffers go to the pool unsynchronised, as the probes have always done; ransac.hip's solver_probe, which used to leak them
+// there instead, now does the same.
+template <typename... B>
+struct DevBufScope {
+    std::tuple<B&...> bufs;
+    explicit DevBufScope(B&... b) : bufs(b...) {}
+    DevBufScope(const DevBufScope&) = delete;
+    ~DevBufScope() { std::apply([](auto&... b) { (b.free(), ...); }, bufs); }
 };
 
 }  // namespace ssfm

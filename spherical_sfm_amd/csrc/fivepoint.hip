@@ -5,33 +5,29 @@
 //   ransac_lib::LocallyOptimizedMSAC<Matrix3d, ..., SteweniusEstimator>::EstimateModel       include/RansacLib/ransac.h:128-275
 //   SteweniusEstimator / FivePointEstimator / PoseFromEssentialMatrix                        evaluation/five_point/*.cpp
 //
-// k_lomsac5_trace is the control flow of k_lomsac_trace (lomsac.hip) for a minimal sample of five: both std::mt19937 streams, the draw /
-// shuffle rule of the sampler, chunks of iterations with one lane per iteration, the chunk walked in order.  What the estimator changes:
+// k_lomsac5_trace runs the control flow of lomsac_trace.h (the one k_lomsac_trace of lomsac.hip runs) for a minimal sample of five.  What the
+// estimator changes:
 //   * up to ten candidate models per minimal sample, scored in two sweeps of five over the rays;
 //   * SteweniusEstimator::NonMinimalSolver returns 0 and LeastSquares is empty, so LocalOptimization and the final least squares change no
 //     model and no score: LocalOptimization is kept for what it still does -- it counts in stats and its LeastSquaresFit shuffles the inlier
 //     list, which advances the local-optimisation stream -- and the final least squares, which re-scores the unchanged model, is dropped;
-//     with it goes the second model: best_model and best_minimal_model are always the same matrix here.
+//     with it goes the second model: best_model and best_minimal_model are always the same matrix here (LO_CHANGES_MODEL = false).
 //   * the tail is estimate_pairwise_five_point's: inlier flags by the epipolar-line residual, acceptance, PoseFromEssentialMatrix.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include "fivepoint_device.h"
+#include "lomsac_trace.h"
 
 namespace ssfm {
 
-constexpr int L5_T = 128;                      // threads per pair (min_num_iterations_ = 100 is one chunk)
-constexpr int L5_FIFO = 5 * L5_T + 64;         // pre-drawn sampler indices (five per iteration + spare for repeated indices)
+constexpr int L5_T = LO_T;                     // threads per pair
 constexpr int L5_RAY_DOUBLES = 5;              // LDS per ray: u0/u2, u1/u2, v0, v1, v2
-constexpr size_t L5_LDS_FIXED = (size_t)(2 * 624 + L5_FIFO) * 4;   // both generator states + the FIFO
+constexpr size_t L5_LDS_FIXED = lo_lds_fixed(5);   // both generator states + the FIFO
 constexpr size_t L5_LDS_BUDGET = 156 * 1024;   // static + dynamic LDS of one workgroup (the CU has 160 KiB)
 
-struct Lo5Opts {
-    double sq_thresh, thresh_mult, success_prob;
-    unsigned min_it, max_it, lo_start;
-    int min_num_inliers, fast_shuffle;
-};
+using Lo5Opts = LoTraceOpts;                   // this estimator has no options of its own
 struct Lo5Shared {                             // static LDS of the trace kernel
     double score[L5_T]; double E[9];
     int sample[5 * L5_T]; int nm[L5_T]; int votes[4]; int cnt; int flag;
@@ -64,6 +60,44 @@ __device__ void l5_local_optimization(const double* model, const FpRays<RAYS_LDS
     block_shuffle_resize(nullptr, ni, 0, mtR, posR, o.fast_shuffle != 0, nullptr, &S->flag);
 }
 
+// what lomsac_trace.h asks of an estimator, over SteweniusEstimator
+template <bool RAYS_LDS>
+struct FivePointTraceEst {
+    static constexpr int K = 5;
+    static constexpr bool LO_CHANGES_MODEL = false;
+    using Shared = Lo5Shared;
+    FpRays<RAYS_LDS> rays; const double* pu; const double* pv; int n; Lo5Opts o; unsigned* mtR; int posR; Lo5Shared* S;
+
+    // MinimalSolver + GetBestEstimatedModelId (ransac.h:184-195, 277-293)
+    __device__ __forceinline__ int solve_and_score(const int* sample, double* myE, double* myScore) const {
+        double u5[15], v5[15];
+        for (int i = 0; i < 5; i++) {
+            const int q = sample[i];
+            for (int k = 0; k < 3; k++) { u5[3 * i + k] = pu[3 * q + k]; v5[3 * i + k] = pv[3 * q + k]; }
+        }
+        double Es[90];
+        const int myNm = fp_minimal_solver(u5, v5, Es);
+        // ScoreModel of the candidates, five per sweep over the rays: a ray is read once per sweep, the five chains are independent
+        for (int m0 = 0; m0 < myNm; m0 += 5) {
+            double Em[5][9], sc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int m = 0; m < 5; m++)
+#pragma unroll
+                for (int k = 0; k < 9; k++) Em[m][k] = (m0 + m < myNm) ? Es[9 * (m0 + m) + k] : 0.0;
+            for (int i = 0; i < n; i++) {
+                double a, b, v0, v1, v2; rays.get(i, &a, &b, &v0, &v1, &v2);
+#pragma unroll
+                for (int m = 0; m < 5; m++) sc[m] += fmin(fp_residual_n(Em[m], a, b, v0, v1, v2), o.sq_thresh);
+            }
+#pragma unroll
+            for (int m = 0; m < 5; m++) if (m0 + m < myNm && sc[m] < *myScore) { *myScore = sc[m]; for (int k = 0; k < 9; k++) myE[k] = Em[m][k]; }
+        }
+        return myNm;
+    }
+    __device__ __forceinline__ void local_optimization(double* model, double*) { l5_local_optimization(model, rays, n, o, mtR, posR, S); }
+    __device__ __forceinline__ int count_inliers(const double* model) { return l5_count_inliers(model, rays, n, o.sq_thresh, &S->cnt); }
+};
+
 template <bool RAYS_LDS>
 __global__ void __launch_bounds__(L5_T, 2)
 k_lomsac5_trace(const int* __restrict__ pair_ptr, const double* __restrict__ gu, const double* __restrict__ gv, Lo5Opts o,
@@ -74,7 +108,7 @@ k_lomsac5_trace(const int* __restrict__ pair_ptr, const double* __restrict__ gu,
     __shared__ Lo5Shared S;
     const int pair = blockIdx.x, tid = threadIdx.x;
     const int r0 = pair_ptr[pair], n = pair_ptr[pair + 1] - r0;
-    const double MAXD = 1.79769313486231570815e308;
+    const double MAXD = LO_MAXD;
     // dynamic LDS: [u0/u2 u1/u2 per ray | v per ray] (RAYS_LDS) then [mtS | mtR | fifo]
     double* sn = lds; double* sv = lds + (size_t)2 * n;
     unsigned* mtS = RAYS_LDS ? reinterpret_cast<unsigned*>(lds + (size_t)L5_RAY_DOUBLES * n) : reinterpret_cast<unsigned*>(lds);
@@ -90,114 +124,9 @@ k_lomsac5_trace(const int* __restrict__ pair_ptr, const double* __restrict__ gu,
 
     double best_model[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     double best_score = MAXD; unsigned it = 0, lo_count = 0;
-    if (n >= 5) {                                                                      // ransac.h:137-141
-        int posS = 624, posR = 624, fifo_head = 0, fifo_cnt = 0;
-        const bool draw = ((double)n / (double)(n - 5)) < 2.71828182845904523536;       // DrawBetterThanShuffle, sampling.h:66-75: n >= 8
-        unsigned max_it = max(o.max_it, o.min_it);
-        auto refresh = [&]() {                                                          // GetInliers(best_model) -> inlier_ratio -> max_num_iterations
-            const int best_num_inliers = l5_count_inliers(best_model, rays, n, o.sq_thresh, &S.cnt);
-            return num_required_iterations((double)best_num_inliers / (double)n, 1.0 - o.success_prob, 5, o.min_it, o.max_it);
-        };
-        bool done = false;
-        while (!done && it < max_it) {
-            unsigned cnt = min((unsigned)L5_T, max_it - it);
-            if (it < o.min_it) cnt = min(cnt, o.min_it - it);                           // never fewer than min_num_iterations_ are run
-            // phase A: the minimal samples of the chunk, in order
-            if (draw) {
-                for (unsigned c = 0; c < cnt; c++) {
-                    int smp[5];
-                    for (int i = 0; i < 5; i++) {
-                        bool found = true;
-                        while (found) {
-                            if (fifo_head >= fifo_cnt) {
-                                __syncthreads();                       // every thread has read the last entry before it is overwritten
-                                fifo_head = 0; fifo_cnt = 0;
-                                while (fifo_cnt < L5_FIFO) {
-                                    if (posS >= 624) { mt_twist(mtS); posS = 0; }
-                                    const int seg = min(L5_FIFO - fifo_cnt, 624 - posS);
-                                    for (int j = tid; j < seg; j += L5_T) { unsigned r; const bool ok = lemire_accept(mt_temper(mtS[posS + j]), (unsigned)n, &r); fifo[fifo_cnt + j] = ok ? (int)r : -1; }
-                                    posS += seg; fifo_cnt += seg;
-                                }
-                                __syncthreads();
-                            }
-                            const int d = fifo[fifo_head++];
-                            if (d < 0) continue;
-                            smp[i] = d; found = false;
-                            for (int j = 0; j < i; j++) if (smp[j] == d) { found = true; break; }
-                        }
-                    }
-                    if (tid == 0) for (int i = 0; i < 5; i++) S.sample[5 * c + i] = smp[i];
-                }
-            } else {
-                // ShuffleSample (sampling.h:104-124): n = 5 takes (0..4) without a draw, n = 6, 7 shuffle (0..n-1) and keep five
-                for (unsigned c = 0; c < cnt; c++) {
-                    int p[7] = {0, 1, 2, 3, 4, 5, 6};
-                    if (n != 5) for (int i = 0; i < n - 1; i++) { const int idx = mt_uniform_int(mtS, posS, i, n - 1); const int t = p[i]; p[i] = p[idx]; p[idx] = t; }
-                    if (tid == 0) for (int i = 0; i < 5; i++) S.sample[5 * c + i] = p[i];
-                }
-            }
-            __syncthreads();
-            // phase B: one lane per iteration -- MinimalSolver + GetBestEstimatedModelId (ransac.h:184-195, 277-293)
-            double myE[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; double myScore = MAXD; int myNm = 0;
-            if ((unsigned)tid < cnt) {
-                double u5[15], v5[15];
-                for (int i = 0; i < 5; i++) {
-                    const int q = S.sample[5 * tid + i];
-                    for (int k = 0; k < 3; k++) { u5[3 * i + k] = pu[3 * q + k]; v5[3 * i + k] = pv[3 * q + k]; }
-                }
-                double Es[90];
-                myNm = fp_minimal_solver(u5, v5, Es);
-                // ScoreModel of the candidates, five per sweep over the rays: a ray is read once per sweep, the five chains are independent
-                for (int m0 = 0; m0 < myNm; m0 += 5) {
-                    double Em[5][9], sc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                    for (int m = 0; m < 5; m++)
-#pragma unroll
-                        for (int k = 0; k < 9; k++) Em[m][k] = (m0 + m < myNm) ? Es[9 * (m0 + m) + k] : 0.0;
-                    for (int i = 0; i < n; i++) {
-                        double a, b, v0, v1, v2; rays.get(i, &a, &b, &v0, &v1, &v2);
-#pragma unroll
-                        for (int m = 0; m < 5; m++) sc[m] += fmin(fp_residual_n(Em[m], a, b, v0, v1, v2), o.sq_thresh);
-                    }
-#pragma unroll
-                    for (int m = 0; m < 5; m++) if (m0 + m < myNm && sc[m] < myScore) { myScore = sc[m]; for (int k = 0; k < 9; k++) myE[k] = Em[m][k]; }
-                }
-            }
-            S.score[tid] = myScore; S.nm[tid] = myNm;
-            __syncthreads();
-            // phase C: the control flow of EstimateModel over the chunk, in order
-            for (unsigned c = 0; c < cnt; c++) {
-                if (it >= max_it) { done = true; break; }
-                if (it == o.lo_start && best_score < MAXD) {                            // ransac.h:160-177
-                    ++lo_count;
-                    l5_local_optimization(best_model, rays, n, o, mtR, posR, &S);
-                    max_it = refresh();
-                }
-                const int nm = S.nm[c]; const double bl = S.score[c];
-                if (nm > 0 && (bl < best_score || it == o.lo_start)) {                  // ransac.h:197-237
-                    const bool best_min_model = bl < best_score;
-                    __syncthreads();
-                    if (best_min_model) {
-                        if ((unsigned)tid == c) for (int k = 0; k < 9; k++) S.E[k] = myE[k];
-                        __syncthreads();
-                        best_score = bl; for (int k = 0; k < 9; k++) best_model[k] = S.E[k];
-                    }
-                    __syncthreads();
-                    const bool run_lo = (it >= o.lo_start && best_score < MAXD);
-                    if (best_min_model || run_lo) {
-                        if (run_lo) { ++lo_count; l5_local_optimization(best_model, rays, n, o, mtR, posR, &S); }
-                        max_it = refresh();
-                    }
-                }
-                ++it;
-            }
-            __syncthreads();
-        }
-        if (it <= o.lo_start && best_score < MAXD) {                                    // ransac.h:241-251
-            ++lo_count;
-            l5_local_optimization(best_model, rays, n, o, mtR, posR, &S);
-        }
-    }
+    FivePointTraceEst<RAYS_LDS> est;
+    est.rays = rays; est.pu = pu; est.pv = pv; est.n = n; est.o = o; est.mtR = mtR; est.posR = 624; est.S = &S;
+    lomsac_trace(est, S, n, o, mtS, fifo, best_model, best_score, it, lo_count);
     // ---- estimate_pairwise_five_point's tail: inlier flags of E (spherical_sfm_tools.cpp:512-520), acceptance and PoseFromEssentialMatrix (:535-561)
     const bool have = (n >= 5) && best_score < MAXD;
     int mine = 0;
@@ -265,26 +194,14 @@ int lomsac5_launch(ssfm_ctx* ctx, hipStream_t st, int num_pairs, int max_n, cons
                    const ssfm_ransac_options& O, double sq_thresh, const unsigned* d_mt_seeded, double* d_E, double* d_score, double* d_R, double* d_t,
                    unsigned char* d_mask, int* d_nin, unsigned* d_stats) {
     Lo5Opts o;
-    o.sq_thresh = sq_thresh; o.thresh_mult = O.threshold_multiplier; o.success_prob = O.success_probability;
-    o.min_it = O.min_num_iterations; o.max_it = O.max_num_iterations; o.lo_start = O.lo_starting_iterations;
-    o.min_num_inliers = O.min_num_inliers; o.fast_shuffle = O.fast_shuffle;
+    lo_trace_opts(O, sq_thresh, &o);
     const bool in_lds = max_n <= l5_max_lds_rays() && !l5_force_global();
     const size_t lds = in_lds ? (size_t)L5_RAY_DOUBLES * max_n * sizeof(double) + L5_LDS_FIXED : L5_LDS_FIXED;
-#define SSFM_L5_LAUNCH(L)                                                                                                                      \
-    do {                                                                                                                                       \
-        if (lds > 48 * 1024) SSFM_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_lomsac5_trace<L>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((k_lomsac5_trace<L>), dim3(num_pairs), dim3(L5_T), lds, st, d_pair_ptr, d_u, d_v, o, d_mt_seeded, d_E, d_score, d_R, d_t, d_mask, d_nin, d_stats); \
-    } while (0)
-    if (in_lds) SSFM_L5_LAUNCH(true); else SSFM_L5_LAUNCH(false);
-#undef SSFM_L5_LAUNCH
-    SSFM_HIP_CHECK(ctx, hipGetLastError());
-    return SSFM_OK;
+    return lo_trace_launch(ctx, st, in_lds ? k_lomsac5_trace<true> : k_lomsac5_trace<false>, num_pairs, lds,
+                           d_pair_ptr, d_u, d_v, o, d_mt_seeded, d_E, d_score, d_R, d_t, d_mask, d_nin, d_stats);
 }
 }  // namespace ssfm
 using namespace ssfm;
-
-static void rm_to_cm(const double* rm, double* cm) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) cm[i + 3 * j] = rm[3 * i + j]; }
-static void cm_to_rm(const double* cm, double* rm) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) rm[3 * i + j] = cm[i + 3 * j]; }
 
 // ---- C ABI: probes -----------------------------------------------------------------------------------------------------------
 extern "C" int32_t ssfm_fivepoint_max_lds_rays(void) { return l5_max_lds_rays(); }
@@ -295,8 +212,9 @@ extern "C" int ssfm_fivepoint_solver_probe(ssfm_ctx* ctx, int32_t n, const doubl
     SSFM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     std::vector<double> hu(u, u + (size_t)3 * n), hv(v, v + (size_t)3 * n), hE((size_t)90 * S); std::vector<int> hs(samples, samples + (size_t)5 * S);
-    DevBuf<double> du, dv, dE; DevBuf<int> ds, dc;
-    auto body = [&]() -> int {
+    {
+        DevBuf<double> du, dv, dE; DevBuf<int> ds, dc;
+        DevBufScope scope(du, dv, dE, ds, dc);
         SSFM_HIP_CHECK(ctx, upload(du, hu, st)); SSFM_HIP_CHECK(ctx, upload(dv, hv, st)); SSFM_HIP_CHECK(ctx, upload(ds, hs, st));
         SSFM_HIP_CHECK(ctx, dE.alloc((size_t)90 * S)); SSFM_HIP_CHECK(ctx, dc.alloc(S));
         hipLaunchKernelGGL(k_fp_solver_probe, dim3((S + 63) / 64), dim3(64), 0, st, S, ds.p, du.p, dv.p, dE.p, dc.p);
@@ -304,11 +222,7 @@ extern "C" int ssfm_fivepoint_solver_probe(ssfm_ctx* ctx, int32_t n, const doubl
         SSFM_HIP_CHECK(ctx, hipMemcpyAsync(hE.data(), dE.p, hE.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         SSFM_HIP_CHECK(ctx, hipMemcpyAsync(counts, dc.p, S * sizeof(int), hipMemcpyDeviceToHost, st));
         SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        return SSFM_OK;
-    };
-    const int rc = body();
-    du.free(); dv.free(); dE.free(); ds.free(); dc.free();
-    if (rc) return rc;
+    }
     for (int s = 0; s < S; s++) for (int m = 0; m < 10; m++) rm_to_cm(&hE[90 * (size_t)s + 9 * m], Es + 90 * (size_t)s + 9 * m);
     return SSFM_OK;
 }
@@ -320,17 +234,13 @@ extern "C" int ssfm_fivepoint_residual_probe(ssfm_ctx* ctx, int32_t n, const dou
     std::vector<double> hu(u, u + (size_t)3 * n), hv(v, v + (size_t)3 * n), hE((size_t)9 * T);
     for (int t = 0; t < T; t++) cm_to_rm(Es + 9 * (size_t)t, &hE[9 * (size_t)t]);
     DevBuf<double> du, dv, dE, derr;
-    auto body = [&]() -> int {
-        SSFM_HIP_CHECK(ctx, upload(du, hu, st)); SSFM_HIP_CHECK(ctx, upload(dv, hv, st)); SSFM_HIP_CHECK(ctx, upload(dE, hE, st)); SSFM_HIP_CHECK(ctx, derr.alloc((size_t)T * n));
-        hipLaunchKernelGGL(k_fp_residual_probe, dim3((n + 255) / 256, T), dim3(256), 0, st, T, n, dE.p, du.p, dv.p, derr.p);
-        SSFM_HIP_CHECK(ctx, hipGetLastError());
-        SSFM_HIP_CHECK(ctx, hipMemcpyAsync(errors, derr.p, (size_t)T * n * sizeof(double), hipMemcpyDeviceToHost, st));
-        SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        return SSFM_OK;
-    };
-    const int rc = body();
-    du.free(); dv.free(); dE.free(); derr.free();
-    return rc;
+    DevBufScope scope(du, dv, dE, derr);
+    SSFM_HIP_CHECK(ctx, upload(du, hu, st)); SSFM_HIP_CHECK(ctx, upload(dv, hv, st)); SSFM_HIP_CHECK(ctx, upload(dE, hE, st)); SSFM_HIP_CHECK(ctx, derr.alloc((size_t)T * n));
+    hipLaunchKernelGGL(k_fp_residual_probe, dim3((n + 255) / 256, T), dim3(256), 0, st, T, n, dE.p, du.p, dv.p, derr.p);
+    SSFM_HIP_CHECK(ctx, hipGetLastError());
+    SSFM_HIP_CHECK(ctx, hipMemcpyAsync(errors, derr.p, (size_t)T * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    return SSFM_OK;
 }
 
 extern "C" int ssfm_fivepoint_pose_probe(ssfm_ctx* ctx, int32_t n, const double* u, const double* v, int32_t tasks, const int32_t* task_ptr, const int32_t* lists,
@@ -344,8 +254,9 @@ extern "C" int ssfm_fivepoint_pose_probe(ssfm_ctx* ctx, int32_t n, const double*
     std::vector<double> hu(u, u + (size_t)3 * n), hv(v, v + (size_t)3 * n), hE((size_t)9 * tasks), hout((size_t)12 * tasks);
     for (int t = 0; t < tasks; t++) cm_to_rm(E + 9 * (size_t)t, &hE[9 * (size_t)t]);
     std::vector<int> hp(task_ptr, task_ptr + tasks + 1), hl(lists, lists + nl), hvotes((size_t)4 * tasks); if (hl.empty()) hl.push_back(0);
-    DevBuf<double> du, dv, dE, dout; DevBuf<int> dp, dl, dvt;
-    auto body = [&]() -> int {
+    {
+        DevBuf<double> du, dv, dE, dout; DevBuf<int> dp, dl, dvt;
+        DevBufScope scope(du, dv, dE, dout, dp, dl, dvt);
         SSFM_HIP_CHECK(ctx, upload(du, hu, st)); SSFM_HIP_CHECK(ctx, upload(dv, hv, st)); SSFM_HIP_CHECK(ctx, upload(dE, hE, st));
         SSFM_HIP_CHECK(ctx, upload(dp, hp, st)); SSFM_HIP_CHECK(ctx, upload(dl, hl, st));
         SSFM_HIP_CHECK(ctx, dout.alloc((size_t)12 * tasks)); SSFM_HIP_CHECK(ctx, dvt.alloc((size_t)4 * tasks));
@@ -354,11 +265,7 @@ extern "C" int ssfm_fivepoint_pose_probe(ssfm_ctx* ctx, int32_t n, const double*
         SSFM_HIP_CHECK(ctx, hipMemcpyAsync(hout.data(), dout.p, hout.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         SSFM_HIP_CHECK(ctx, hipMemcpyAsync(hvotes.data(), dvt.p, hvotes.size() * sizeof(int), hipMemcpyDeviceToHost, st));
         SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        return SSFM_OK;
-    };
-    const int rc = body();
-    du.free(); dv.free(); dE.free(); dout.free(); dp.free(); dl.free(); dvt.free();
-    if (rc) return rc;
+    }
     for (int t = 0; t < tasks; t++) {
         if (R_out) rm_to_cm(&hout[12 * (size_t)t], R_out + 9 * (size_t)t);
         if (t_out) for (int k = 0; k < 3; k++) t_out[3 * (size_t)t + k] = hout[12 * (size_t)t + 9 + k];

@@ -16,24 +16,23 @@
 // depend on the models, so its draws can run ahead; the models of a lane are scored against every ray); the control flow then walks the
 // chunk in order, and the rare events (a new best minimal model, the local optimisation at iteration lo_starting_iterations_, the
 // final least squares) are workgroup-cooperative: ordered inlier compaction, block-wide scores, a block-wide Levenberg-Marquardt.
-// 128 threads per pair: RansacLib never stops before min_num_iterations_ = 100 and usually stops there, so the first chunk is those
-// 100 iterations.
+// The control flow itself (chunks, the sampler running ahead, the ordered walk) is lomsac_trace.h's; this file is the estimator.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include "ransac_device.h"
+#include "lomsac_trace.h"
 #include "sampson_lsq.h"
 
 namespace ssfm {
 
-constexpr int LO_T = 128;          // threads per pair
-constexpr int LO_FIFO = 3 * LO_T + 64;   // pre-drawn sampler indices (three per iteration + spare for repeated indices)
-
-struct LoOpts {
-    double sq_thresh, thresh_mult, success_prob;
-    unsigned min_it, max_it, lo_start;
-    int num_lo_steps, num_lsq_it, min_sample_mult, non_min_mult, final_lsq, inward, min_num_inliers, fast_shuffle;
+struct LoOpts : LoTraceOpts {
+    int num_lo_steps, num_lsq_it, min_sample_mult, non_min_mult, final_lsq, inward;
 };
+// dynamic LDS of k_lomsac_trace: [rays u | rays v] (3 n doubles each), [listA | listB] (n ints each) and `pad` ints (rays resident only),
+// then lo_lds_fixed(3).  The kernel pads by n & 1, which keeps what follows 8-byte aligned; a launch is sized with pad = 2 for its largest pair.
+constexpr size_t lo_lds_front(int n, int pad) { return (size_t)6 * n * 8 + (size_t)(2 * n + pad) * 4; }
+constexpr size_t lo_lds_bytes(int max_n) { return lo_lds_front(max_n, 2) + lo_lds_fixed(3); }
+constexpr size_t LO_LDS_BUDGET = 150 * 1024;
 
 // SphericalEstimator::NonMinimalSolver (src/spherical_estimator.cpp:86-108): the action-matrix solver on 4..9 rays, the candidate with
 // the least Sampson sum over the sample wins (first of equals).  One thread runs it.
@@ -80,7 +79,6 @@ __device__ void lo_lsq_fit(LoState& st, double thresh, double* model) {
     block_shuffle_resize(st.listB, ni, sz, st.mtR, st.posR, st.o.fast_shuffle != 0, st.S->dr, &st.S->flag);
     lo_wave_lsq(st.listB, sz, st.pu, st.pv, st.o.inward != 0, model, st.S);
 }
-__device__ __forceinline__ void lo_update(double sc, const double* m, double* best_sc, double* best) { if (sc < *best_sc) { *best_sc = sc; for (int k = 0; k < 9; k++) best[k] = m[k]; } }
 
 // LocalOptimization (ransac.h:341-407)
 __device__ void lo_local_optimization(LoState& st, double* best_min, double* score_best) {
@@ -118,6 +116,61 @@ __device__ void lo_local_optimization(LoState& st, double* best_min, double* sco
     }
 }
 
+// what lomsac_trace.h asks of an estimator, over SphericalEstimator
+template <bool POLY>
+struct SphericalTraceEst {
+    static constexpr int K = 3;
+    static constexpr bool LO_CHANGES_MODEL = true;
+    using Shared = LoShared;
+    // the rays and the threshold beside st: st goes to lo_local_optimization by reference, so what is read through it is read from memory through a
+    // generic pointer, and the sweep over the rays must see them where the kernel put them (LDS)
+    const double* pu; const double* pv; int n; double sq_thresh; LoShared* S; LoState* st;
+
+    // MinimalSolver + GetBestEstimatedModelId (ransac.h:184-195, 277-293)
+    __device__ __forceinline__ int solve_and_score(const int* sample, double* myE, double* myScore) const {
+        double u3[9], v3[9];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            const int q = sample[i];
+#pragma unroll
+            for (int k = 0; k < 3; k++) { u3[3 * i + k] = pu[3 * q + k]; v3[3 * i + k] = pv[3 * q + k]; }
+        }
+        double B[6][3], Es[36];
+        spherical_nullspace<3>(u3, v3, 3, B);
+        const int myNm = spherical_models_from_basis<POLY, true>(B, Es);
+        if (myNm == 4) {
+            // ScoreModel of the four candidates in ONE sweep over the rays: a ray is read from LDS once (a broadcast read) and
+            // the four independent chains fill the FP64 pipe; the quotient by hardware reciprocal + two Newton steps
+            double sc[4] = {0.0, 0.0, 0.0, 0.0};
+            for (int i = 0; i < n; i++) {
+                const double u0 = pu[3 * i], u1 = pu[3 * i + 1], u2 = pu[3 * i + 2], v0 = pv[3 * i], v1 = pv[3 * i + 1], v2 = pv[3 * i + 2];
+#pragma unroll
+                for (int m = 0; m < 4; m++) {
+                    const double* E = Es + 9 * m;
+                    const double e0 = E[0] * u0 + E[1] * u1 + E[2] * u2, e1 = E[3] * u0 + E[4] * u1 + E[5] * u2, e2 = E[6] * u0 + E[7] * u1 + E[8] * u2;
+                    const double f0 = E[0] * v0 + E[3] * v1 + E[6] * v2, f1 = E[1] * v0 + E[4] * v1 + E[7] * v2;
+                    const double d = v0 * e0 + v1 * e1 + v2 * e2;
+                    sc[m] += fmin((d * d) * fast_rcp(e0 * e0 + e1 * e1 + f0 * f0 + f1 * f1), sq_thresh);
+                }
+            }
+#pragma unroll
+            for (int m = 0; m < 4; m++) if (sc[m] < *myScore) { *myScore = sc[m]; for (int k = 0; k < 9; k++) myE[k] = Es[9 * m + k]; }
+        }
+        return myNm;
+    }
+    __device__ __forceinline__ void local_optimization(double* model, double* score) { lo_local_optimization(*st, model, score); }
+    __device__ __forceinline__ int count_inliers(const double* model) {
+        double c[1] = {0.0};
+        for (int i = threadIdx.x; i < n; i += LO_T) c[0] += (sampson_err(model, pu + 3 * i, pv + 3 * i) < sq_thresh) ? 1.0 : 0.0;
+        block_sum<1>(c, S->red);
+        if (threadIdx.x == 0) S->bc = c[0];
+        __syncthreads();
+        const int r = (int)S->bc;
+        __syncthreads();
+        return r;
+    }
+};
+
 template <bool POLY, bool RAYS_LDS>
 __global__ void __launch_bounds__(LO_T, 2)
 k_lomsac_trace(const int* __restrict__ pair_ptr, const double* __restrict__ gu, const double* __restrict__ gv, LoOpts o,
@@ -128,11 +181,10 @@ k_lomsac_trace(const int* __restrict__ pair_ptr, const double* __restrict__ gu, 
     __shared__ LoShared S;
     const int pair = blockIdx.x, tid = threadIdx.x;
     const int r0 = pair_ptr[pair], n = pair_ptr[pair + 1] - r0;
-    const double MAXD = 1.79769313486231570815e308;
-    // dynamic LDS: [rays u | rays v | listA | listB] (RAYS_LDS) then [mtS | mtR | fifo]
+    // dynamic LDS: lo_lds_front (RAYS_LDS) then [mtS | mtR | fifo]
     double* su = lds; double* sv = lds + (size_t)3 * n;
     int* lA = reinterpret_cast<int*>(lds + (size_t)6 * n); int* lB = lA + n;
-    unsigned* mtS = RAYS_LDS ? reinterpret_cast<unsigned*>(lB + n + (n & 1)) : reinterpret_cast<unsigned*>(lds);
+    unsigned* mtS = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(lds) + (RAYS_LDS ? lo_lds_front(n, n & 1) : 0));
     unsigned* mtR = mtS + 624; int* fifo = reinterpret_cast<int*>(mtR + 624);
     const double* pu; const double* pv; int* listA; int* listB;
     if (RAYS_LDS) {
@@ -143,150 +195,21 @@ k_lomsac_trace(const int* __restrict__ pair_ptr, const double* __restrict__ gu, 
     __syncthreads();
 
     double best_model[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    double best_score = MAXD; int best_num_inliers = 0; unsigned it = 0, lo_count = 0;
-    if (n >= 3) {                                                                      // ransac.h:137-141
-        LoState st; st.pu = pu; st.pv = pv; st.n = n; st.listA = listA; st.listB = listB; st.mtR = mtR; st.posR = 624; st.S = &S; st.o = o;
-        int posS = 624, fifo_head = 0, fifo_cnt = 0;
-        const bool draw = ((double)n / (double)(n - 3)) < 2.71828182845904523536;       // DrawBetterThanShuffle, sampling.h:66-75
-        unsigned max_it = max(o.max_it, o.min_it);
-        double best_min[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; double best_min_score = MAXD;
-        auto refresh_inliers = [&]() {
-            // GetInliers(best_model) -> best_num_inliers, inlier_ratio -> max_num_iterations  (ransac.h:169-176, 229-236)
-            double c[1] = {0.0};
-            for (int i = tid; i < n; i += LO_T) c[0] += (sampson_err(best_model, pu + 3 * i, pv + 3 * i) < o.sq_thresh) ? 1.0 : 0.0;
-            block_sum<1>(c, S.red);
-            if (tid == 0) S.bc = c[0];
-            __syncthreads();
-            best_num_inliers = (int)S.bc;
-            __syncthreads();
-        };
-        bool done = false;
-        while (!done && it < max_it) {
-            // ---- chunk of iterations [it, it + cnt)
-            unsigned cnt = min((unsigned)LO_T, max_it - it);
-            if (it < o.min_it) cnt = min(cnt, o.min_it - it);                           // never fewer than min_num_iterations_ are run
-            // phase A: the minimal samples of the chunk, in order (the sampler's stream is independent of everything else)
-            if (draw) {
-                for (unsigned c = 0; c < cnt; c++) {
-                    int smp[3];
-                    for (int i = 0; i < 3; i++) {
-                        bool found = true;
-                        while (found) {
-                            if (fifo_head >= fifo_cnt) {
-                                // refill: temper the next words of the stream in parallel; -1 marks a Lemire rejection (the draw is repeated)
-                                __syncthreads();                       // every thread has read the last entry before it is overwritten
-                                fifo_head = 0; fifo_cnt = 0;
-                                while (fifo_cnt < LO_FIFO) {
-                                    if (posS >= 624) { mt_twist(mtS); posS = 0; }
-                                    const int seg = min(LO_FIFO - fifo_cnt, 624 - posS);
-                                    for (int j = tid; j < seg; j += LO_T) { unsigned r; const bool ok = lemire_accept(mt_temper(mtS[posS + j]), (unsigned)n, &r); fifo[fifo_cnt + j] = ok ? (int)r : -1; }
-                                    posS += seg; fifo_cnt += seg;
-                                }
-                                __syncthreads();
-                            }
-                            const int d = fifo[fifo_head++];
-                            if (d < 0) continue;
-                            smp[i] = d; found = false;
-                            for (int j = 0; j < i; j++) if (smp[j] == d) { found = true; break; }
-                        }
-                    }
-                    if (tid == 0) { S.sample[3 * c] = smp[0]; S.sample[3 * c + 1] = smp[1]; S.sample[3 * c + 2] = smp[2]; }
-                }
-            } else {
-                // ShuffleSample (sampling.h:104-124): n = 3 takes (0,1,2) without a draw, n = 4 shuffles (0,1,2,3) and keeps three
-                for (unsigned c = 0; c < cnt; c++) {
-                    int p[4] = {0, 1, 2, 3};
-                    if (n != 3) for (int i = 0; i < n - 1; i++) { const int idx = mt_uniform_int(mtS, posS, i, n - 1); const int t = p[i]; p[i] = p[idx]; p[idx] = t; }
-                    if (tid == 0) { S.sample[3 * c] = p[0]; S.sample[3 * c + 1] = p[1]; S.sample[3 * c + 2] = p[2]; }
-                }
-            }
-            __syncthreads();
-            // phase B: one lane per iteration -- MinimalSolver + GetBestEstimatedModelId (ransac.h:184-195, 277-293)
-            double myE[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; double myScore = MAXD; int myNm = 0;
-            if ((unsigned)tid < cnt) {
-                double u3[9], v3[9];
-#pragma unroll
-                for (int i = 0; i < 3; i++) {
-                    const int q = S.sample[3 * tid + i];
-#pragma unroll
-                    for (int k = 0; k < 3; k++) { u3[3 * i + k] = pu[3 * q + k]; v3[3 * i + k] = pv[3 * q + k]; }
-                }
-                double B[6][3], Es[36];
-                spherical_nullspace<3>(u3, v3, 3, B);
-                myNm = spherical_models_from_basis<POLY, true>(B, Es);
-                if (myNm == 4) {
-                    // ScoreModel of the four candidates in ONE sweep over the rays: a ray is read from LDS once (a broadcast read) and
-                    // the four independent chains fill the FP64 pipe; the quotient by hardware reciprocal + two Newton steps
-                    double sc[4] = {0.0, 0.0, 0.0, 0.0};
-                    for (int i = 0; i < n; i++) {
-                        const double u0 = pu[3 * i], u1 = pu[3 * i + 1], u2 = pu[3 * i + 2], v0 = pv[3 * i], v1 = pv[3 * i + 1], v2 = pv[3 * i + 2];
-#pragma unroll
-                        for (int m = 0; m < 4; m++) {
-                            const double* E = Es + 9 * m;
-                            const double e0 = E[0] * u0 + E[1] * u1 + E[2] * u2, e1 = E[3] * u0 + E[4] * u1 + E[5] * u2, e2 = E[6] * u0 + E[7] * u1 + E[8] * u2;
-                            const double f0 = E[0] * v0 + E[3] * v1 + E[6] * v2, f1 = E[1] * v0 + E[4] * v1 + E[7] * v2;
-                            const double d = v0 * e0 + v1 * e1 + v2 * e2;
-                            sc[m] += fmin((d * d) * fast_rcp(e0 * e0 + e1 * e1 + f0 * f0 + f1 * f1), o.sq_thresh);
-                        }
-                    }
-#pragma unroll
-                    for (int m = 0; m < 4; m++) if (sc[m] < myScore) { myScore = sc[m]; for (int k = 0; k < 9; k++) myE[k] = Es[9 * m + k]; }
-                }
-            }
-            S.score[tid] = myScore; S.nm[tid] = myNm;
-            __syncthreads();
-            // phase C: the control flow of EstimateModel over the chunk, in order
-            for (unsigned c = 0; c < cnt; c++) {
-                if (it >= max_it) { done = true; break; }
-                if (it == o.lo_start && best_min_score < MAXD) {                        // ransac.h:160-177
-                    ++lo_count;
-                    lo_local_optimization(st, best_model, &best_score);
-                    refresh_inliers();
-                    max_it = num_required_iterations((double)best_num_inliers / (double)n, 1.0 - o.success_prob, 3, o.min_it, o.max_it);
-                }
-                const int nm = S.nm[c]; const double bl = S.score[c];
-                if (nm > 0 && (bl < best_min_score || it == o.lo_start)) {              // ransac.h:197-237
-                    const bool best_min_model = bl < best_min_score;
-                    __syncthreads();
-                    if (best_min_model) {
-                        if ((unsigned)tid == c) for (int k = 0; k < 9; k++) S.E[k] = myE[k];
-                        __syncthreads();
-                        best_min_score = bl; for (int k = 0; k < 9; k++) best_min[k] = S.E[k];
-                        lo_update(best_min_score, best_min, &best_score, best_model);
-                    }
-                    __syncthreads();
-                    const bool run_lo = (it >= o.lo_start && best_min_score < MAXD);
-                    if (best_min_model || run_lo) {
-                        if (run_lo) {
-                            ++lo_count;
-                            double sc = best_min_score;
-                            lo_local_optimization(st, best_min, &sc);
-                            lo_update(sc, best_min, &best_score, best_model);
-                        }
-                        refresh_inliers();
-                        max_it = num_required_iterations((double)best_num_inliers / (double)n, 1.0 - o.success_prob, 3, o.min_it, o.max_it);
-                    }
-                }
-                ++it;
-            }
-            __syncthreads();
-        }
-        if (it <= o.lo_start && best_score < MAXD) {                                    // ransac.h:241-251
-            ++lo_count;
-            lo_local_optimization(st, best_model, &best_score);
-            refresh_inliers();
-        }
-        if (o.final_lsq) {                                                              // ransac.h:253-270
-            double refined[9]; for (int k = 0; k < 9; k++) refined[k] = best_model[k];
-            // stats.inlier_indices is GetInliers(best_model) of the last update; LeastSquares on an empty list still rebuilds E from r
-            const int ni = block_inlier_list(best_model, pu, pv, n, o.sq_thresh, listB, S.cnt);
-            lo_wave_lsq(listB, ni, pu, pv, o.inward != 0, refined, &S);
-            const double sc = block_msac_score(refined, pu, pv, n, o.sq_thresh, S.red, &S.bc);
-            if (sc < best_score) { best_score = sc; for (int k = 0; k < 9; k++) best_model[k] = refined[k]; refresh_inliers(); }
-        }
+    double best_score = LO_MAXD; unsigned it = 0, lo_count = 0;
+    LoState st; st.pu = pu; st.pv = pv; st.n = n; st.listA = listA; st.listB = listB; st.mtR = mtR; st.posR = 624; st.S = &S; st.o = o;
+    SphericalTraceEst<POLY> est{pu, pv, n, o.sq_thresh, &S, &st};
+    lomsac_trace(est, S, n, o, mtS, fifo, best_model, best_score, it, lo_count);
+    if (n >= 3 && o.final_lsq) {                                                        // ransac.h:253-270
+        double refined[9]; for (int k = 0; k < 9; k++) refined[k] = best_model[k];
+        // stats.inlier_indices is GetInliers(best_model) of the last update; LeastSquares on an empty list still rebuilds E from r
+        const int ni = block_inlier_list(best_model, pu, pv, n, o.sq_thresh, listB, S.cnt);
+        lo_wave_lsq(listB, ni, pu, pv, o.inward != 0, refined, &S);
+        const double sc = block_msac_score(refined, pu, pv, n, o.sq_thresh, S.red, &S.bc);
+        // (the count of GetInliers is not read any more: the call is kept only for the barriers and the work the kernel has always had here)
+        if (sc < best_score) { best_score = sc; for (int k = 0; k < 9; k++) best_model[k] = refined[k]; (void)est.count_inliers(best_model); }
     }
     // ---- estimate_pairwise's tail: inlier flags of E (spherical_sfm_tools.cpp:388-392), acceptance and Decompose (:410-419)
-    const bool have = (n >= 3) && best_score < MAXD;
+    const bool have = (n >= 3) && best_score < LO_MAXD;
     double cnt[1] = {0.0};
     for (int i = tid; i < n; i += LO_T) {
         const bool in = have && sampson_err(best_model, pu + 3 * i, pv + 3 * i) < o.sq_thresh;
@@ -301,7 +224,6 @@ k_lomsac_trace(const int* __restrict__ pair_ptr, const double* __restrict__ gu, 
         outScore[pair] = best_score;
         if (stats) { stats[2 * (size_t)pair] = it; stats[2 * (size_t)pair + 1] = lo_count; }
     }
-    (void)best_num_inliers;
 }
 
 // ---- deterministic probes of the pieces (tests/test_ransac_probes_gpu.py) -------------------------------------------------------
@@ -385,38 +307,21 @@ k_mt_probe(const unsigned* __restrict__ seeded, int n, const int* __restrict__ l
 }  // namespace ssfm
 using namespace ssfm;
 
-static void rm_to_cm(const double* rm, double* cm) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) cm[i + 3 * j] = rm[3 * i + j]; }
-static void cm_to_rm(const double* cm, double* rm) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) rm[3 * i + j] = cm[i + 3 * j]; }
-
 // One slab of pairs through the trace kernel; device buffers are the caller's.  Used by ransac.hip's batch driver.
 namespace ssfm {
+bool lomsac_needs_global_lists(int max_n) { return lo_lds_bytes(max_n) > LO_LDS_BUDGET; }
 int lomsac_launch(ssfm_ctx* ctx, hipStream_t st, int num_pairs, int max_n, const int* d_pair_ptr, const double* d_u, const double* d_v, int total,
                   const ssfm_ransac_options& O, double sq_thresh, const unsigned* d_mt_seeded, int* d_lists, double* d_E, double* d_score, double* d_R,
                   unsigned char* d_mask, int* d_nin, unsigned* d_stats) {
     LoOpts o;
-    o.sq_thresh = sq_thresh; o.thresh_mult = O.threshold_multiplier; o.success_prob = O.success_probability;
-    o.min_it = O.min_num_iterations; o.max_it = O.max_num_iterations; o.lo_start = O.lo_starting_iterations;
+    lo_trace_opts(O, sq_thresh, &o);
     o.num_lo_steps = O.num_lo_steps; o.num_lsq_it = O.num_lsq_iterations; o.min_sample_mult = O.min_sample_multiplicator;
-    o.non_min_mult = O.non_min_sample_multiplier; o.final_lsq = O.final_least_squares; o.inward = O.inward; o.min_num_inliers = O.min_num_inliers;
-    o.fast_shuffle = O.fast_shuffle;
-    const size_t fixed = (size_t)(2 * 624 + LO_FIFO) * 4;
-    const size_t lds_rays = (size_t)6 * max_n * 8 + (size_t)(2 * max_n + 2) * 4 + fixed;
-    const bool in_lds = lds_rays <= 150 * 1024;
-    const size_t lds = in_lds ? lds_rays : fixed;
+    o.non_min_mult = O.non_min_sample_multiplier; o.final_lsq = O.final_least_squares; o.inward = O.inward;
+    const bool in_lds = !lomsac_needs_global_lists(max_n);
+    const size_t lds = in_lds ? lo_lds_bytes(max_n) : lo_lds_fixed(3);
     (void)total;
-#define SSFM_LO_LAUNCH(P, L)                                                                                                                   \
-    do {                                                                                                                                       \
-        if (lds > 48 * 1024) SSFM_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_lomsac_trace<P, L>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((k_lomsac_trace<P, L>), dim3(num_pairs), dim3(LO_T), lds, st, d_pair_ptr, d_u, d_v, o, d_mt_seeded, d_lists, d_E, d_score, d_R, d_mask, d_nin, d_stats); \
-    } while (0)
-    if (O.use_poly_solver) { if (in_lds) SSFM_LO_LAUNCH(true, true); else SSFM_LO_LAUNCH(true, false); }
-    else { if (in_lds) SSFM_LO_LAUNCH(false, true); else SSFM_LO_LAUNCH(false, false); }
-#undef SSFM_LO_LAUNCH
-    SSFM_HIP_CHECK(ctx, hipGetLastError());
-    return SSFM_OK;
-}
-bool lomsac_needs_global_lists(int max_n) {
-    return (size_t)6 * max_n * 8 + (size_t)(2 * max_n + 2) * 4 + (size_t)(2 * 624 + LO_FIFO) * 4 > 150 * 1024;
+    auto kernel = O.use_poly_solver ? (in_lds ? k_lomsac_trace<true, true> : k_lomsac_trace<true, false>) : (in_lds ? k_lomsac_trace<false, true> : k_lomsac_trace<false, false>);
+    return lo_trace_launch(ctx, st, kernel, num_pairs, lds, d_pair_ptr, d_u, d_v, o, d_mt_seeded, d_lists, d_E, d_score, d_R, d_mask, d_nin, d_stats);
 }
 }  // namespace ssfm
 
@@ -433,20 +338,15 @@ static int estimator_probe(ssfm_ctx* ctx, int what, int32_t n, const double* u, 
     if (E_cm) for (int t = 0; t < tasks; t++) cm_to_rm(E_cm + 9 * (size_t)t, &hE[9 * (size_t)t]);
     std::vector<int> hp(task_ptr, task_ptr + tasks + 1), hl(lists, lists + std::max(nl, 0)); if (hl.empty()) hl.push_back(0);
     DevBuf<double> du, dv, dE, dout; DevBuf<int> dp, dl;
-    int rc = SSFM_OK;
-    auto body = [&]() -> int {
-        SSFM_HIP_CHECK(ctx, upload(du, hu, st)); SSFM_HIP_CHECK(ctx, upload(dv, hv, st)); SSFM_HIP_CHECK(ctx, upload(dE, hE, st));
-        SSFM_HIP_CHECK(ctx, upload(dp, hp, st)); SSFM_HIP_CHECK(ctx, upload(dl, hl, st)); SSFM_HIP_CHECK(ctx, dout.alloc((size_t)EST_OUT * tasks));
-        const size_t lds = (size_t)maxc * 4 + 16;
-        if (lds > 48 * 1024) SSFM_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_estimator_probe), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_estimator_probe, dim3(tasks), dim3(LO_T), lds, st, what, n, du.p, dv.p, dp.p, dl.p, dE.p, inward, dout.p);
-        SSFM_HIP_CHECK(ctx, hipMemcpyAsync(out12, dout.p, (size_t)EST_OUT * tasks * sizeof(double), hipMemcpyDeviceToHost, st));
-        SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        return SSFM_OK;
-    };
-    rc = body();
-    du.free(); dv.free(); dE.free(); dout.free(); dp.free(); dl.free();
-    return rc;
+    DevBufScope scope(du, dv, dE, dout, dp, dl);
+    SSFM_HIP_CHECK(ctx, upload(du, hu, st)); SSFM_HIP_CHECK(ctx, upload(dv, hv, st)); SSFM_HIP_CHECK(ctx, upload(dE, hE, st));
+    SSFM_HIP_CHECK(ctx, upload(dp, hp, st)); SSFM_HIP_CHECK(ctx, upload(dl, hl, st)); SSFM_HIP_CHECK(ctx, dout.alloc((size_t)EST_OUT * tasks));
+    const size_t lds = (size_t)maxc * 4 + 16;
+    if (lds > 48 * 1024) SSFM_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_estimator_probe), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_estimator_probe, dim3(tasks), dim3(LO_T), lds, st, what, n, du.p, dv.p, dp.p, dl.p, dE.p, inward, dout.p);
+    SSFM_HIP_CHECK(ctx, hipMemcpyAsync(out12, dout.p, (size_t)EST_OUT * tasks * sizeof(double), hipMemcpyDeviceToHost, st));
+    SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    return SSFM_OK;
 }
 
 extern "C" int ssfm_sampson_refine_probe(ssfm_ctx* ctx, int32_t n, const double* u, const double* v, int32_t tasks, const int32_t* task_ptr,
@@ -504,17 +404,14 @@ extern "C" int ssfm_so3_probe(ssfm_ctx* ctx, int32_t what, int32_t n, const doub
     std::vector<double> hin(nin), hout(nout);
     // matrices cross the ABI column-major; the kernels are row-major
     if (vec_in) std::memcpy(hin.data(), in, nin * sizeof(double)); else for (int i = 0; i < n; i++) cm_to_rm(in + 9 * (size_t)i, &hin[9 * (size_t)i]);
-    DevBuf<double> din, dout;
-    auto body = [&]() -> int {
+    {
+        DevBuf<double> din, dout;
+        DevBufScope scope(din, dout);
         SSFM_HIP_CHECK(ctx, upload(din, hin, st)); SSFM_HIP_CHECK(ctx, dout.alloc(nout));
         hipLaunchKernelGGL(k_so3_probe, dim3((n + 63) / 64), dim3(64), 0, st, what, n, din.p, dout.p);
         SSFM_HIP_CHECK(ctx, hipMemcpyAsync(hout.data(), dout.p, nout * sizeof(double), hipMemcpyDeviceToHost, st));
         SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        return SSFM_OK;
-    };
-    const int rc = body();
-    din.free(); dout.free();
-    if (rc) return rc;
+    }
     if (vec_in) for (int i = 0; i < n; i++) rm_to_cm(&hout[9 * (size_t)i], out + 9 * (size_t)i); else std::memcpy(out, hout.data(), nout * sizeof(double));
     return SSFM_OK;
 }
@@ -527,18 +424,14 @@ extern "C" int ssfm_mt19937_probe(ssfm_ctx* ctx, uint32_t seed, int32_t n, const
     std::vector<unsigned> seeded(624); mt_seed_host(seed, seeded.data());
     std::vector<int> hlo(lo, lo + n), hhi(hi, hi + n); if (hlo.empty()) { hlo.push_back(0); hhi.push_back(0); }
     DevBuf<unsigned> ds, draw; DevBuf<int> dlo, dhi, dout;
-    auto body = [&]() -> int {
-        SSFM_HIP_CHECK(ctx, upload(ds, seeded, st)); SSFM_HIP_CHECK(ctx, upload(dlo, hlo, st)); SSFM_HIP_CHECK(ctx, upload(dhi, hhi, st));
-        SSFM_HIP_CHECK(ctx, dout.alloc(std::max(n, 1))); SSFM_HIP_CHECK(ctx, draw.alloc(std::max(nraw, 1)));
-        hipLaunchKernelGGL(k_mt_probe, dim3(1), dim3(LO_T), 0, st, ds.p, n, dlo.p, dhi.p, dout.p, draw.p, nraw);
-        if (n > 0) SSFM_HIP_CHECK(ctx, hipMemcpyAsync(draws, dout.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
-        if (nraw > 0) SSFM_HIP_CHECK(ctx, hipMemcpyAsync(raw, draw.p, (size_t)nraw * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-        SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        return SSFM_OK;
-    };
-    const int rc = body();
-    ds.free(); draw.free(); dlo.free(); dhi.free(); dout.free();
-    return rc;
+    DevBufScope scope(ds, draw, dlo, dhi, dout);
+    SSFM_HIP_CHECK(ctx, upload(ds, seeded, st)); SSFM_HIP_CHECK(ctx, upload(dlo, hlo, st)); SSFM_HIP_CHECK(ctx, upload(dhi, hhi, st));
+    SSFM_HIP_CHECK(ctx, dout.alloc(std::max(n, 1))); SSFM_HIP_CHECK(ctx, draw.alloc(std::max(nraw, 1)));
+    hipLaunchKernelGGL(k_mt_probe, dim3(1), dim3(LO_T), 0, st, ds.p, n, dlo.p, dhi.p, dout.p, draw.p, nraw);
+    if (n > 0) SSFM_HIP_CHECK(ctx, hipMemcpyAsync(draws, dout.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (nraw > 0) SSFM_HIP_CHECK(ctx, hipMemcpyAsync(raw, draw.p, (size_t)nraw * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    return SSFM_OK;
 }
 
 extern "C" int ssfm_minimal_solver_probe(ssfm_ctx* ctx, int32_t n, const double* u, const double* v, int32_t S, const int32_t* samples, int32_t use_poly_solver,
@@ -548,8 +441,9 @@ extern "C" int ssfm_minimal_solver_probe(ssfm_ctx* ctx, int32_t n, const double*
     SSFM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     std::vector<double> hu(u, u + (size_t)3 * n), hv(v, v + (size_t)3 * n), hE((size_t)36 * S); std::vector<int> hs(samples, samples + (size_t)3 * S);
-    DevBuf<double> du, dv, dE; DevBuf<int> ds, dc;
-    auto body = [&]() -> int {
+    {
+        DevBuf<double> du, dv, dE; DevBuf<int> ds, dc;
+        DevBufScope scope(du, dv, dE, ds, dc);
         SSFM_HIP_CHECK(ctx, upload(du, hu, st)); SSFM_HIP_CHECK(ctx, upload(dv, hv, st)); SSFM_HIP_CHECK(ctx, upload(ds, hs, st));
         SSFM_HIP_CHECK(ctx, dE.alloc((size_t)36 * S)); SSFM_HIP_CHECK(ctx, dc.alloc(S));
         if (use_poly_solver) hipLaunchKernelGGL(k_minimal_all_probe<true>, dim3((S + 63) / 64), dim3(64), 0, st, S, 3, ds.p, du.p, dv.p, dE.p, dc.p);
@@ -557,11 +451,7 @@ extern "C" int ssfm_minimal_solver_probe(ssfm_ctx* ctx, int32_t n, const double*
         SSFM_HIP_CHECK(ctx, hipMemcpyAsync(hE.data(), dE.p, hE.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         SSFM_HIP_CHECK(ctx, hipMemcpyAsync(counts, dc.p, S * sizeof(int), hipMemcpyDeviceToHost, st));
         SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        return SSFM_OK;
-    };
-    const int rc = body();
-    du.free(); dv.free(); dE.free(); ds.free(); dc.free();
-    if (rc) return rc;
+    }
     for (int s = 0; s < S; s++) for (int m = 0; m < 4; m++) rm_to_cm(&hE[36 * (size_t)s + 9 * m], Es + 36 * (size_t)s + 9 * m);
     return SSFM_OK;
 }
@@ -573,16 +463,12 @@ extern "C" int ssfm_sampson_probe(ssfm_ctx* ctx, int32_t n, const double* u, con
     std::vector<double> hu(u, u + (size_t)3 * n), hv(v, v + (size_t)3 * n), hE((size_t)9 * T);
     for (int t = 0; t < T; t++) cm_to_rm(Es + 9 * (size_t)t, &hE[9 * (size_t)t]);
     DevBuf<double> du, dv, dE, derr;
-    auto body = [&]() -> int {
-        SSFM_HIP_CHECK(ctx, upload(du, hu, st)); SSFM_HIP_CHECK(ctx, upload(dv, hv, st)); SSFM_HIP_CHECK(ctx, upload(dE, hE, st)); SSFM_HIP_CHECK(ctx, derr.alloc((size_t)T * n));
-        hipLaunchKernelGGL(k_sampson_probe, dim3((n + 255) / 256, T), dim3(256), 0, st, T, n, dE.p, du.p, dv.p, derr.p);
-        SSFM_HIP_CHECK(ctx, hipMemcpyAsync(errors, derr.p, (size_t)T * n * sizeof(double), hipMemcpyDeviceToHost, st));
-        SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        return SSFM_OK;
-    };
-    const int rc = body();
-    du.free(); dv.free(); dE.free(); derr.free();
-    return rc;
+    DevBufScope scope(du, dv, dE, derr);
+    SSFM_HIP_CHECK(ctx, upload(du, hu, st)); SSFM_HIP_CHECK(ctx, upload(dv, hv, st)); SSFM_HIP_CHECK(ctx, upload(dE, hE, st)); SSFM_HIP_CHECK(ctx, derr.alloc((size_t)T * n));
+    hipLaunchKernelGGL(k_sampson_probe, dim3((n + 255) / 256, T), dim3(256), 0, st, T, n, dE.p, du.p, dv.p, derr.p);
+    SSFM_HIP_CHECK(ctx, hipMemcpyAsync(errors, derr.p, (size_t)T * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
+    return SSFM_OK;
 }
 
 // ---- C ABI: the reference's estimator interface for ONE pair, rays resident on the device ---------------------------------------

@@ -193,8 +193,6 @@ k_focal_trials(int n, int E, const int* __restrict__ e0, const int* __restrict__
 }  // namespace ssfm
 using namespace ssfm;
 
-static void rm_to_cm(const double* rm, double* cm) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) cm[i + 3 * j] = rm[3 * i + j]; }
-
 extern "C" void ssfm_ransac_default_options(ssfm_ransac_options* o) {
     o->num_hypotheses = 1024;          // mode 0 only: fixed budget per pair
     o->seed = 0;                       // RansacOptions::random_seed_
@@ -655,6 +653,7 @@ static int solver_probe(ssfm_ctx* ctx, bool poly, int32_t n, const double* u, co
     SSFM_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     DevBuf<double> du, dv, dE; DevBuf<int> ds, dc;
+    DevBufScope scope(du, dv, dE, ds, dc);
     std::vector<double> hu(u, u + (size_t)3 * n), hv(v, v + (size_t)3 * n); std::vector<int> hs(samples, samples + (size_t)3 * S);
     SSFM_HIP_CHECK(ctx, upload(du, hu, st)); SSFM_HIP_CHECK(ctx, upload(dv, hv, st)); SSFM_HIP_CHECK(ctx, upload(ds, hs, st));
     SSFM_HIP_CHECK(ctx, dE.alloc((size_t)36 * S)); SSFM_HIP_CHECK(ctx, dc.alloc(S));
@@ -665,7 +664,6 @@ static int solver_probe(ssfm_ctx* ctx, bool poly, int32_t n, const double* u, co
     SSFM_HIP_CHECK(ctx, hipMemcpyAsync(counts, dc.p, S * sizeof(int), hipMemcpyDeviceToHost, st));
     SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));
     for (int s = 0; s < S; s++) for (int m = 0; m < 4; m++) rm_to_cm(&hE[36 * (size_t)s + 9 * m], Es + 36 * (size_t)s + 9 * m);
-    du.free(); dv.free(); dE.free(); ds.free(); dc.free();
     return SSFM_OK;
 }
 extern "C" int ssfm_spherical_solver_probe(ssfm_ctx* ctx, int32_t n, const double* u, const double* v, int32_t S, const int32_t* samples,

@@ -42,6 +42,9 @@ SSFM_HD void mat3_tvec(const double* A, const double* x, double* y) {         //
 SSFM_HD void cross3(const double* a, const double* b, double* c) {
     c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
 }
+// 3x3 matrices cross the C ABI column-major (Eigen's default); everything inside is row-major
+SSFM_HD void rm_to_cm(const double* rm, double* cm) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) cm[i + 3 * j] = rm[3 * i + j]; }
+SSFM_HD void cm_to_rm(const double* cm, double* rm) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) rm[3 * i + j] = cm[i + 3 * j]; }
 SSFM_HD double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 SSFM_HD double norm3(const double* a) { return sqrt(dot3(a, a)); }
 

@@ -154,9 +154,6 @@ k_focal_trials_graph(int n, int E, const int* __restrict__ e0, const int* __rest
 }  // namespace ssfm
 using namespace ssfm;
 
-static void cm_to_rm(const double* cm, double* rm) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) rm[3 * i + j] = cm[i + 3 * j]; }
-static void rm_to_cm(const double* rm, double* cm) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) cm[i + 3 * j] = rm[3 * i + j]; }
-
 // the device buffers of one record slab stay within the bound the match path uses for its slot buffer (match.hip: 64 MB); SSFM_TRIPLET_SLAB_RECORDS (read at
 // every call, like SSFM_MATCH_SLAB_PAIRS) overrides the record count of a slab, so that a small problem can walk the multi-slab path
 static const size_t kRecordSlabBytes = (size_t)64 << 20;

@@ -161,6 +161,35 @@ def test_trace_equals_the_replay(gpu_ctx):
         assert rep["accepted"] and _rot_err_deg(out["R"][k], probs[k][2]) < 2.0
 
 
+# ---- 4b. the branches of the control flow that the default options hardly reach ------------------------------------------------------
+# (lomsac_trace.h) the local optimisation at the first iteration, inside the first chunk, on a chunk boundary and never before the tail; chunks shorter
+# than min_num_iterations_; a one-iteration second chunk; a fixed budget across three chunks; a budget that ends before lo_starting_iterations_
+TRACE_OPTION_GRID = [dict(lo_start=0), dict(lo_start=1), dict(lo_start=127), dict(lo_start=128), dict(lo_start=100000), dict(min_it=1, lo_start=0),
+                     dict(min_it=20, lo_start=50), dict(min_it=129), dict(min_it=300, max_it=300, lo_start=256), dict(min_it=10, max_it=10, lo_start=50)]
+OPTION_FIELD = dict(min_it="min_num_iterations", max_it="max_num_iterations", lo_start="lo_starting_iterations")
+
+
+@functools.lru_cache(maxsize=None)
+def grid_pairs():
+    """two pairs of 12 correspondences without outliers, two of 40 with 50 % outliers (377 and 496 iterations with the default options: three and four
+    chunks, the later ones refill the sampler's FIFO), with the replay of each under every option set (about a second per replay)"""
+    probs = [synth.make_general_pose_problem(n, noise_px=0.5, outlier_frac=frac, focal=FOCAL, seed=seed) for n, frac in ((12, 0.0), (40, 0.5)) for seed in (900, 901)]
+    reps = [[F.replay(p[0], p[1], THR, **opts) for p in probs] for opts in TRACE_OPTION_GRID]
+    return probs, reps
+
+
+def test_rarely_taken_branches_of_the_control_flow(gpu_ctx):
+    probs, reps = grid_pairs()
+    ptr, U, V = _flat([(p[0], p[1]) for p in probs])
+    for opts, rep4 in zip(TRACE_OPTION_GRID, reps):
+        out = ransac.ransac5_batch(gpu_ctx, ptr, U, V, THR, **{OPTION_FIELD[k]: v for k, v in opts.items()})
+        for k, rep in enumerate(rep4):
+            print(opts, k, "iterations", out["iterations"][k], rep["iterations"], "lo runs", out["lo_runs"][k], rep["lo_runs"], "inliers", out["num_inliers"][k], rep["num_inliers"],
+                  "E %.2e" % F.sign_distance(out["E"][k], rep["E"]))
+            assert not rep["marginal"], (opts, k)                # chosen on the CPU: the replay flags none of the 40 cases
+            _check_against_replay(out, k, ptr, rep, SOLVER_TOL)
+
+
 # ---- 5. small and odd shapes, both ray placements ------------------------------------------------------------------------------------
 def test_small_shapes_and_both_ray_placements(gpu_ctx, monkeypatch):
     big_n = ransac.fivepoint_max_lds_rays() + 1                # the first size whose rays stay in global memory, from the kernel's own layout

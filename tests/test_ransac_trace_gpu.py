@@ -196,6 +196,35 @@ def test_trace_mode_with_local_optimization_steps(gpu_ctx, oracle, poly):
     assert res[:, 0].mean() >= 0.95 and res[:, 1].mean() >= 0.95 and res[:, 2].mean() >= 0.95, res.mean(axis=0)
 
 
+# The branches of the control flow that the default options hardly reach (lomsac_trace.h): the local optimisation at the first iteration, inside the
+# first chunk, on a chunk boundary and never before the tail; chunks shorter than min_num_iterations_; a one-iteration second chunk; a fixed budget
+# across three chunks; a budget that ends before lo_starting_iterations_.  Keys are ssfm_ransac_options fields.
+TRACE_OPTION_GRID = [dict(lo_starting_iterations=0), dict(lo_starting_iterations=1), dict(lo_starting_iterations=127), dict(lo_starting_iterations=128),
+                     dict(lo_starting_iterations=100000), dict(min_num_iterations=1, lo_starting_iterations=0),
+                     dict(min_num_iterations=20, lo_starting_iterations=50), dict(min_num_iterations=129),
+                     dict(min_num_iterations=300, max_num_iterations=300, lo_starting_iterations=256),
+                     dict(min_num_iterations=10, max_num_iterations=10, lo_starting_iterations=50)]
+# two pairs of 12 correspondences without outliers, two of 40 with 50 % outliers.  The seeds of the larger two are chosen on the CPU: with the default
+# options the oracle runs them for 211 and 171 iterations (both solvers), so their second chunk refills the sampler's FIFO
+GRID_PAIRS = [(12, 0.0, 900), (12, 0.0, 901), (40, 0.5, 1098), (40, 0.5, 955)]
+
+
+@pytest.mark.parametrize("poly", [False, True])
+def test_rarely_taken_branches_of_the_control_flow(gpu_ctx, oracle, poly):
+    from spherical_sfm_amd import ransac
+    probs = [synth.make_relative_pose_problem(n, seed=seed, noise=1 / 600, outlier_frac=frac) for n, frac, seed in GRID_PAIRS]
+    for opts in TRACE_OPTION_GRID:
+        out = ransac.estimate_pairs(gpu_ctx, [(p[0], p[1]) for p in probs], THR, use_poly_solver=int(poly), **opts)
+        refs = [oracle.lomsac_pair(p[0], p[1], THR, use_poly=poly, min_iterations=opts.get("min_num_iterations", 100),
+                                   max_iterations=opts.get("max_num_iterations", 10000), lo_starting_iterations=opts.get("lo_starting_iterations", 50)) for p in probs]
+        for k, (p, o) in enumerate(zip(probs, refs)):
+            print(opts, poly, k, "iterations", out["iterations"][k], o["iterations"], "lo runs", out["lo_runs"][k], o["lo_runs"], "inliers", out["num_inliers"][k], o["num_inliers"],
+                  "E %.2e R %.2e" % (frob_err(out["E"][k], o["E"]), rot_err(out["R"][k], o["R"])))
+            assert _compare(out, k, o, p[0], p[1], oracle, tol=1e-9) == (True, True, True), (opts, k)
+        if opts.get("max_num_iterations", 10000) > 128:
+            assert max(o["iterations"] for o in refs[2:]) > 128, opts                   # a second chunk, with a refill of the FIFO
+
+
 def test_fast_shuffle_is_the_same_stream(gpu_ctx):
     from spherical_sfm_amd import ransac
     probs = _pairs(12, 400, 0.3, 1 / 600, seed0=700)
