@@ -736,10 +736,13 @@ __device__ __forceinline__ void gram_gather(const double* __restrict__ A, const 
         if (e < K * PER) dst[k * STRIDE + i] = v[it];
     }
 }
-// Round 5, FUSE (every point of the problem sits in a signature group): the kernel also does k_point_lin's work -- the lanes of a point fold their V = sum Jp^T Jp, g_p and
-// focal coupling over the K observation lanes (three xor exchanges), every lane damps and inverts the 3x3 block itself, lane 0 of the point stores the record PS and g_p
-// for the back substitution and the wave adds the five point-pass sums (cost, focal sums) and the gradient maximum to its scalar slot at the end.  k_point_lin does not
-// run then (15.5 us of a 173 us iteration at config 2, 180 of 1550 at the configs[4] size), PS is not read back and the observations are read one pass less.
+// FUSE (every point of the problem sits in a signature group): the task also does k_point_lin's work for its own points, ONCE, in a prologue in front of the sub-chunk
+// loop -- one lane per point in rounds of 64, the K observations of the point in k_point_lin's order and arithmetic against the camera records the task has just staged
+// in LDS (a wave-uniform record address: an LDS broadcast where k_point_lin makes dependent global gathers), damping, sym3_inverse, the 12-double record PS and g_p to
+// global memory for the back substitution.  The sub-chunk loop then reads PS back as the unfused kernel does (the same wave wrote it: a workgroup-scope fence, no
+// agent-scope one) and stays instruction for instruction what it was; the wave adds the five point-pass sums (cost, focal sums) and the gradient maximum to its scalar
+// slot at the end.  k_point_lin does not run then.  Round 5 had this work INSIDE the loop, a lane per observation: every observation linearised twice, 12 doubles folded
+// over the observation lanes per sub-chunk, all 64 lanes inverting the same eight blocks -- 2.3 x the loop's vector instructions (profiles/r09_notes.md).
 // spec (speculative launch behind k_publish, like k_point_lin's): [go, radius] as decided on the device.
 struct GramFuse { const double* scale_pt; double radius, min_diag, max_diag; double* PS_out; double* gp_out; double* scal; const double* spec; int emit_skip = 0; };
 // one wave task of k_schur_gram / k_schur_gram_any (below): the task's tile shape (NT, TI) is a template parameter, the task index an argument
@@ -770,6 +773,76 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
     gram_gather<33, GRAM_CAMREC, 6>(cam, rot, camv, K, lane, sCam);
     { const int k = min(lane / DC, K - 1), c = gram_cam_of(camv, k); const double sc = scale_cam[6 * c + off + lane - DC * (lane / DC)]; if (lane < DC * K) sScale[lane] = sc; }
     if (lane < GRAM_NPAIR + GRAM_KMAX) sSlot[lane] = rec[12 + lane];
+    const double sf = scale_f[0];
+    if constexpr (FUSE) {
+        double pacc[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, pgmax = 0.0;         // cost, FJJ, FJR, FWW, FWG of this lane's points; gradient maximum
+        // ---- the point pass of the task's points (k_point_lin), before the camera sums and the tile accumulators are alive
+        constexpr int KC = ((16 * NT + (TI > 0 ? 4 : 0)) / DC < GRAM_KMAX) ? (16 * NT + (TI > 0 ? 4 : 0)) / DC : GRAM_KMAX;      // the longest camera list of this tile class
+        wave_lds_handover();                                             // sCam is written
+        for (int r0 = 0; r0 < cnt; r0 += 64) {
+            const bool valid = r0 + lane < cnt;
+            const int q = min(r0 + lane, cnt - 1);                       // (past the end: the last point again, nothing stored, nothing summed)
+            const size_t p = (size_t)(p0 + q);
+            const double2* op = obs_xy + (j00 + (size_t)q * K);
+            double Xp[3], sp[3]; double2 oo[KC];
+#pragma unroll
+            for (int k = 0; k < 3; k++) { Xp[k] = pts[3 * p + k]; sp[k] = fz.scale_pt[3 * p + k]; }
+#pragma unroll
+            for (int k = 0; k < KC; k++) oo[k] = op[min(k, K - 1)];      // every observation of the point in flight at once
+            double Vd[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0}, wf[3] = {0, 0, 0}, a0 = 0.0, a1 = 0.0, a2 = 0.0;
+#pragma unroll
+            for (int k = 0; k < KC; k++)
+                if (k < K) {                                             // wave-uniform
+                    const double* crec = sCam + k * GRAM_CAMREC;
+                    ObsPoint L; lin_obs_point(f, crec, crec + 6, Xp, oo[k].x, oo[k].y, loss, la, L);
+                    a0 += L.half_rho;
+#pragma unroll
+                    for (int a = 0; a < 2; a++) {
+                        const double j0 = L.Jp[a][0] * sp[0], j1 = L.Jp[a][1] * sp[1], j2 = L.Jp[a][2] * sp[2], jf = L.Jf[a] * sf;
+                        Vd[0] += j0 * j0; Vd[1] += j0 * j1; Vd[2] += j0 * j2; Vd[3] += j1 * j1; Vd[4] += j1 * j2; Vd[5] += j2 * j2;
+                        g[0] += j0 * L.r[a]; g[1] += j1 * L.r[a]; g[2] += j2 * L.r[a];
+                        wf[0] += jf * j0; wf[1] += jf * j1; wf[2] += jf * j2;
+                        a1 += jf * jf; a2 += jf * L.r[a];
+                    }
+                }
+            double gm = 0.0;
+            if (sp[0] > 0.0) {
+                gm = fmax(fabs(g[0] / sp[0]), fmax(fabs(g[1] / sp[1]), fabs(g[2] / sp[2])));
+                Vd[0] += fmin(fmax(Vd[0], fz.min_diag), fz.max_diag) / fz_radius;
+                Vd[3] += fmin(fmax(Vd[3], fz.min_diag), fz.max_diag) / fz_radius;
+                Vd[5] += fmin(fmax(Vd[5], fz.min_diag), fz.max_diag) / fz_radius;
+            } else { Vd[0] = Vd[3] = Vd[5] = 1.0; }                       // constant point: identity block, zero coupling
+            double Vi[6]; sym3_inverse(Vd, Vi);
+            const double u0 = wf[0] * Vi[0] + wf[1] * Vi[1] + wf[2] * Vi[2];
+            const double u1 = wf[0] * Vi[1] + wf[1] * Vi[3] + wf[2] * Vi[4];
+            const double u2 = wf[0] * Vi[2] + wf[1] * Vi[4] + wf[2] * Vi[5];
+            if (valid) {
+                pacc[0] += a0; pacc[1] += a1; pacc[2] += a2;
+                pacc[3] += u0 * wf[0] + u1 * wf[1] + u2 * wf[2];
+                pacc[4] += u0 * g[0] + u1 * g[1] + u2 * g[2];
+                pgmax = fmax(pgmax, gm);
+                double* ps = fz.PS_out + 12 * p;                          // the record of k_point_lin: [ diag(s) V^-1 diag(s) (6) | s o (V^-1 g) (3) | s o (V^-1 w_f) (3) ]
+                ps[0] = Vi[0] * sp[0] * sp[0]; ps[1] = Vi[1] * sp[0] * sp[1]; ps[2] = Vi[2] * sp[0] * sp[2];
+                ps[3] = Vi[3] * sp[1] * sp[1]; ps[4] = Vi[4] * sp[1] * sp[2]; ps[5] = Vi[5] * sp[2] * sp[2];
+                ps[6] = sp[0] * (Vi[0] * g[0] + Vi[1] * g[1] + Vi[2] * g[2]); ps[7] = sp[1] * (Vi[1] * g[0] + Vi[3] * g[1] + Vi[4] * g[2]);
+                ps[8] = sp[2] * (Vi[2] * g[0] + Vi[4] * g[1] + Vi[5] * g[2]);
+                ps[9] = sp[0] * u0; ps[10] = sp[1] * u1; ps[11] = sp[2] * u2;
+#pragma unroll
+                for (int k = 0; k < 3; k++) fz.gp_out[3 * p + k] = g[k];
+            }
+        }
+        {                                                                // the point pass's sums and gradient maximum, one wave = one scalar slot (k_point_lin's rule); here and
+            const double t = wave_transpose_sum(pacc);                   // not at the end of the task: twelve registers less across the sub-chunk loop
+            pgmax = wave_max(pgmax);
+            const int slot = wave_tr_index();
+            double* sl = fz.scal + (size_t)(task & (SC_NSLOT - 1)) * SC_TOTAL;
+            if (slot < 5) unsafeAtomicAdd(&sl[slot], t);
+            if (lane == 0 && pgmax > 0.0) atomic_max_nonneg(&sl[SC_GMAX], pgmax);
+        }
+        // the loop below reads PS back on other lanes of this wave: the stores have left before the first load is issued
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_s_waitcnt(0x0F70 /* vmcnt(0) */); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    const double* PSr = FUSE ? (const double*)fz.PS_out : PS;            // (FUSE: through the pointer the prologue stored through -- PS is declared __restrict__)
     v4d_ acc[NT * (NT + 1) / 2];
 #pragma unroll
     for (int t = 0; t < NT * (NT + 1) / 2; t++) acc[t] = v4d_{0.0, 0.0, 0.0, 0.0};
@@ -785,20 +858,14 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
     const int li = lane & 15, lk = lane >> 4;                          // fragment / accumulator coordinates of the tiles
     const int lp = lane & (GRAM_SUB - 1), lq = lane >> 3;               // linearisation: point of the sub-chunk, observation (= camera of the group) of this lane
     const int kq = min(lq, K - 1);                                      // clamped: a lane whose camera does not exist repeats the last one, stores nothing and sums nothing
-    const double sf = scale_f[0];
     // point record of a sub-chunk: X, the scaled V^-1 (6) with V^-1 g (3) and V^-1 w_f (3), this lane's observation
     double X[3], V[12]; double2 ob;
-    double spt[3] = {0.0, 0.0, 0.0};                                     // FUSE: Jacobi scales of the point (what k_point_lin read)
-    double pacc[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, pgmax = 0.0;             // FUSE: cost, FJJ, FJR, FWW, FWG of this lane; gradient maximum
 #define GRAM_LOAD(s0_)                                                                                                            \
     do {                                                                                                                          \
         const int q_ = min((s0_) + lp, cnt - 1);                                                                                  \
         _Pragma("unroll") for (int k = 0; k < 3; k++) X[k] = pts[3 * (size_t)(p0 + q_) + k];                                      \
-        if (FUSE) { _Pragma("unroll") for (int k = 0; k < 3; k++) spt[k] = fz.scale_pt[3 * (size_t)(p0 + q_) + k]; }              \
-        else {                                                                                                                    \
-        _Pragma("unroll") for (int k = 0; k < 9; k++) V[k] = PS[12 * (size_t)(p0 + q_) + k];                                      \
-        if (focal_free) { _Pragma("unroll") for (int k = 9; k < 12; k++) V[k] = PS[12 * (size_t)(p0 + q_) + k]; }                 \
-        }                                                                                                                         \
+        _Pragma("unroll") for (int k = 0; k < 9; k++) V[k] = PSr[12 * (size_t)(p0 + q_) + k];                                     \
+        if (focal_free) { _Pragma("unroll") for (int k = 9; k < 12; k++) V[k] = PSr[12 * (size_t)(p0 + q_) + k]; }                \
         ob = obs_xy[j00 + (size_t)q_ * K + kq];                                                                                   \
     } while (0)
     GRAM_LOAD(0);
@@ -808,51 +875,6 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
         {
             const bool valid = s0 + lp < cnt;
             const double* crec = sCam + kq * GRAM_CAMREC;
-            if (FUSE) {
-                // the point pass (k_point_lin): this lane's observation through the point-side view of the linearisation FIRST (r, J_f, J_p: 11 values; the camera blocks
-                // are formed afterwards, so that they are not alive during the fold -- together with the 39 camera sums and the tile accumulators they spilled 49-80 registers),
-                // folded over the K lanes of its point
-                const double wgt = (valid && lq < K) ? 1.0 : 0.0;
-                double pv[12];
-                {
-                    ObsPoint Lp; lin_obs_point(f, crec, crec + 6, X, ob.x, ob.y, loss, la, Lp);
-                    double j0[2], j1[2], j2[2], jf[2];
-#pragma unroll
-                    for (int a = 0; a < 2; a++) { j0[a] = Lp.Jp[a][0] * spt[0] * wgt; j1[a] = Lp.Jp[a][1] * spt[1] * wgt; j2[a] = Lp.Jp[a][2] * spt[2] * wgt; jf[a] = Lp.Jf[a] * sf * wgt; }
-                    pv[0] = j0[0] * j0[0] + j0[1] * j0[1]; pv[1] = j0[0] * j1[0] + j0[1] * j1[1]; pv[2] = j0[0] * j2[0] + j0[1] * j2[1];
-                    pv[3] = j1[0] * j1[0] + j1[1] * j1[1]; pv[4] = j1[0] * j2[0] + j1[1] * j2[1]; pv[5] = j2[0] * j2[0] + j2[1] * j2[1];
-                    pv[6] = j0[0] * Lp.r[0] + j0[1] * Lp.r[1]; pv[7] = j1[0] * Lp.r[0] + j1[1] * Lp.r[1]; pv[8] = j2[0] * Lp.r[0] + j2[1] * Lp.r[1];
-                    pv[9] = jf[0] * j0[0] + jf[1] * j0[1]; pv[10] = jf[0] * j1[0] + jf[1] * j1[1]; pv[11] = jf[0] * j2[0] + jf[1] * j2[1];
-                    pacc[0] += wgt * Lp.half_rho; pacc[1] += jf[0] * jf[0] + jf[1] * jf[1]; pacc[2] += jf[0] * Lp.r[0] + jf[1] * Lp.r[1];
-                }
-#pragma unroll
-                for (int i = 0; i < 12; i++) { double t = pv[i]; t += __shfl_xor(t, 8, 64); t += __shfl_xor(t, 16, 64); t += __shfl_xor(t, 32, 64); pv[i] = t; }
-                double Vd[6] = {pv[0], pv[1], pv[2], pv[3], pv[4], pv[5]};
-                if (spt[0] > 0.0) {
-                    if (valid && lq == 0) pgmax = fmax(pgmax, fmax(fabs(pv[6] / spt[0]), fmax(fabs(pv[7] / spt[1]), fabs(pv[8] / spt[2]))));
-                    Vd[0] += fmin(fmax(Vd[0], fz.min_diag), fz.max_diag) / fz_radius;
-                    Vd[3] += fmin(fmax(Vd[3], fz.min_diag), fz.max_diag) / fz_radius;
-                    Vd[5] += fmin(fmax(Vd[5], fz.min_diag), fz.max_diag) / fz_radius;
-                } else { Vd[0] = Vd[3] = Vd[5] = 1.0; }                   // constant point: identity block, zero coupling
-                double Vi[6]; sym3_inverse(Vd, Vi);
-                const double u0 = pv[9] * Vi[0] + pv[10] * Vi[1] + pv[11] * Vi[2];
-                const double u1 = pv[9] * Vi[1] + pv[10] * Vi[3] + pv[11] * Vi[4];
-                const double u2 = pv[9] * Vi[2] + pv[10] * Vi[4] + pv[11] * Vi[5];
-                V[0] = Vi[0] * spt[0] * spt[0]; V[1] = Vi[1] * spt[0] * spt[1]; V[2] = Vi[2] * spt[0] * spt[2];
-                V[3] = Vi[3] * spt[1] * spt[1]; V[4] = Vi[4] * spt[1] * spt[2]; V[5] = Vi[5] * spt[2] * spt[2];
-                V[6] = spt[0] * (Vi[0] * pv[6] + Vi[1] * pv[7] + Vi[2] * pv[8]); V[7] = spt[1] * (Vi[1] * pv[6] + Vi[3] * pv[7] + Vi[4] * pv[8]);
-                V[8] = spt[2] * (Vi[2] * pv[6] + Vi[4] * pv[7] + Vi[5] * pv[8]);
-                V[9] = spt[0] * u0; V[10] = spt[1] * u1; V[11] = spt[2] * u2;
-                if (valid && lq == 0) {
-                    pacc[3] += u0 * pv[9] + u1 * pv[10] + u2 * pv[11];
-                    pacc[4] += u0 * pv[6] + u1 * pv[7] + u2 * pv[8];
-                    double* ps = fz.PS_out + 12 * (size_t)(p0 + s0 + lp);
-#pragma unroll
-                    for (int k = 0; k < 12; k++) ps[k] = V[k];
-#pragma unroll
-                    for (int k = 0; k < 3; k++) fz.gp_out[3 * (size_t)(p0 + s0 + lp) + k] = pv[6 + k];
-                }
-            }
             ObsLin Lk; lin_obs<DC == 6>(f, crec, crec + 6, X, ob.x, ob.y, loss, la, Lk);
             // Cholesky factor of the scaled V^-1 (all zero for a fixed point or a lane past the end of the task: its columns of Y are zero)
             double L00 = 0, L10 = 0, L20 = 0, L11 = 0, L21 = 0, L22 = 0;
@@ -1049,14 +1071,6 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
             } else if (PB) PB[idx] = v;
             else zadd(dz, &(S_val + (size_t)sDiag[a] * BB)[e], v);
         }
-    }
-    if (FUSE) {                                                          // the point pass's sums and gradient maximum, one wave = one scalar slot (k_point_lin's rule)
-        const double t = wave_transpose_sum(pacc);
-        pgmax = wave_max(pgmax);
-        const int slot = wave_tr_index();
-        double* sl = fz.scal + (size_t)(task & (SC_NSLOT - 1)) * SC_TOTAL;
-        if (slot < 5) unsafeAtomicAdd(&sl[slot], t);
-        if (lane == 0 && pgmax > 0.0) atomic_max_nonneg(&sl[SC_GMAX], pgmax);
     }
     if (dbg && lane == 0) { long long* d = dbg + 4 * (size_t)task; d[0] = t_0; d[1] = t_1; d[2] = t_2; d[3] = wall_clock64(); }   // SSFM_GRAM_STAMPS (timing study)
 }

@@ -152,12 +152,13 @@ struct LmRun {
         spec_on = poll && nP > 0 && knob_env_int("SSFM_LM_SPECULATE", 1) != 0;
         gram_bs = knob_env_int("SSFM_GRAM_BACKSUB", -1);             // 0 / 1 forces k_gram_backsub2 off / on (back_substitute)
         gbs_split_env = knob_env_int("SSFM_GBS_SPLIT", 0);           // > 0: waves per task of k_gram_backsub2
-        // Round 5 EXPERIMENT, off (SSFM_GRAM_FUSE=1): when every point sits in a signature group, k_schur_gram does the point pass itself (ba_kernels.h: FUSE) and k_point_lin
-        // does not run; the speculative launch behind k_publish is then the Gram kernel of the NEXT iteration, accumulating into the next zone.  Correct (parity 3e-11, same
-        // iterations) and SLOWER: 97.6 us against 43.7 + 18.3 at config 2, 1357 against 409 + 179 at the configs[4] size -- the Gram kernel sits at its register limit
-        // (256 at two waves per SIMD: 39 camera sums, the tile accumulators, one observation's linearisation) and the point pass's fold spills 43-80 of them to scratch
-        // (profiles/r05_notes.md).  One launch less is not worth a kernel that leaves its registers.
-        fuse_lin = SSFM_LAB_KNOB("SSFM_GRAM_FUSE", 0) != 0 && nP > 0 && !F.gr_rec.empty() && F.gram_points == (int64_t)nP && F.chunk_cam.empty() && F.cs_task_cam.empty();
+        // Every point in a signature group, one Gram launch per tile class and nothing else in the assembly: the Gram task does the point pass of its own points in a
+        // prologue (ba_kernels.h: FUSE) and k_point_lin does not run; the speculative launch behind k_publish is then the Gram kernel of the NEXT iteration, accumulating
+        // into the next zone.  Not with pair or camera-sum tasks (they read PS of points other tasks own), not in the mixed-class k_schur_gram_any launch, not with
+        // SSFM_DETERMINISTIC=1 (the fused epilogue adds its sums with plain atomics).  SSFM_GRAM_FUSE=0: k_point_lin + the unfused kernel (profiles/r09_notes.md).
+        { int cls_end[5]; const int n_cls = gram_classes(cls_end);
+          fuse_lin = knob_env_int("SSFM_GRAM_FUSE", 1) != 0 && !h->det && nP > 0 && !F.gr_rec.empty() && F.gram_points == (int64_t)nP && F.chunk_cam.empty() && F.cs_task_cam.empty()
+                     && !(F.gram_any && n_cls > 1) && cls_end[4] == cls_end[3]; }      // (no task of the three-tile class: gram_kernel_of)
         return SSFM_OK;
     }
 
@@ -253,43 +254,43 @@ struct LmRun {
     // the kernel of a tile class (launch_gram)
     using GramKernel = decltype(&k_schur_gram<DC, 1, 0, false>);
     template <bool FUSE> static GramKernel gram_kernel_of(int cls) {
-        static const GramKernel k[5] = {k_schur_gram<DC, 1, 0, FUSE>, k_schur_gram<DC, 1, 2, FUSE>, k_schur_gram<DC, 2, 0, FUSE>, k_schur_gram<DC, 2, 3, FUSE>, k_schur_gram<DC, 3, 0, FUSE>};
+        // (FUSE: the three-tile class has no fused form -- k_schur_gram<6, 3, 0> sits at its 256 registers and the prologue costs it 16 B more scratch; read_knobs keeps
+        //  k_point_lin for a problem with such tasks.  3-dof cameras never reach the classes behind the third.)
+        static const GramKernel k[5] = {k_schur_gram<DC, 1, 0, FUSE>, k_schur_gram<DC, 1, 2, FUSE>, k_schur_gram<DC, 2, 0, FUSE>, k_schur_gram<DC, 2, 3, FUSE && DC == 6>, k_schur_gram<DC, 3, 0, false>};
         return k[cls];
     }
-    GramKernel gram_kernel(int cls) const {
-#ifdef SSFM_LAB
-        if (fuse_lin) return gram_kernel_of<true>(cls);
-#endif
-        return gram_kernel_of<false>(cls);
+    GramKernel gram_kernel(int cls) const { return fuse_lin ? gram_kernel_of<true>(cls) : gram_kernel_of<false>(cls); }
+    // one launch per tile class (the tasks are sorted by K, i.e. by rows = DC K): rows <= 16 -> 1 row tile of 16; 17..20 -> 1 tile + a tail of <= 4 rows through
+    // the 4x4x4 instruction; <= 32 -> 2 tiles; 33..36 -> 2 tiles + tail; else 3 tiles.  cls_end[cl] = end of class cl's task range; returns the classes in use
+    static bool gram_t4() { return SSFM_LAB_KNOB("SSFM_GRAM_T4", 1) != 0; }
+    int gram_classes(int (&cls_end)[5]) const {
+        const int ng = (int)(F.gr_rec.size() / GRAM_REC);
+        const bool t4 = gram_t4();
+        auto tile_class = [&](int K) { const int rows = DC * K; return rows <= 16 ? 0 : (rows <= 20 && t4) ? 1 : rows <= 32 ? 2 : (rows <= 36 && t4) ? 3 : 4; };
+        for (int cl = 0; cl < 5; cl++) cls_end[cl] = 0;
+        for (int t = 0; t < ng; t++) { const int c0 = tile_class(F.gr_rec[(size_t)t * GRAM_REC + 2]); for (int cl = c0; cl < 5; cl++) cls_end[cl] = t + 1; }
+        int n_cls = 0; for (int cl = 0; cl < 5; cl++) if (cls_end[cl] > (cl ? cls_end[cl - 1] : 0)) n_cls++;
+        return n_cls;
     }
     // signature groups: Gram products on the matrix cores (ba_kernels.h: k_schur_gram); one launch per tile class.  at = the state it linearises at,
     // z = the zone it accumulates into, spec = device-side [go, radius] of a speculative launch (fused point pass only)
     int launch_gram(const State& at, const ZoneView& z, const double* spec) {
         const int ng = (int)(F.gr_rec.size() / GRAM_REC);
-        const bool gram_t4 = SSFM_LAB_KNOB("SSFM_GRAM_T4", 1) != 0;
         const int gram_waves = std::min(4, std::max(1, SSFM_LAB_KNOB("SSFM_GRAM_WAVES", 1)));   // waves (tasks) per workgroup: 1 measured best (2: +14 %, 4: +13 % at the configs[4] size)
         long long* gram_dbg = nullptr;
 #ifdef SSFM_LAB
         gram_dbg = lab_gram_stamps_begin(ng);
 #endif
-        // one launch per tile class (the tasks are sorted by K, i.e. by rows = DC K): rows <= 16 -> 1 row tile of 16; 17..20 -> 1 tile + a tail of <= 4 rows through
-        // the 4x4x4 instruction; <= 32 -> 2 tiles; 33..36 -> 2 tiles + tail; else 3 tiles
-        auto tile_class = [&](int K) { const int rows = DC * K; return rows <= 16 ? 0 : (rows <= 20 && gram_t4) ? 1 : rows <= 32 ? 2 : (rows <= 36 && gram_t4) ? 3 : 4; };
-        int cls_end[5] = {0, 0, 0, 0, 0};
-        for (int t = 0; t < ng; t++) { const int c0 = tile_class(F.gr_rec[(size_t)t * GRAM_REC + 2]); for (int cl = c0; cl < 5; cl++) cls_end[cl] = t + 1; }
-        int n_cls = 0; for (int cl = 0; cl < 5; cl++) if (cls_end[cl] > (cl ? cls_end[cl - 1] : 0)) n_cls++;
+        int cls_end[5]; const int n_cls = gram_classes(cls_end);
         const bool gram_any = F.gram_any;                                 // SSFM_GRAM_ANY as the PLAN read it (one value for the cost model and the launch; 0: one launch per tile class)
-        bool any_ok = gram_any && n_cls > 1 && gram_waves == 1 && !gram_dbg;
-#ifdef SSFM_LAB
-        any_ok = any_ok && !fuse_lin;
-#endif
+        const bool any_ok = gram_any && n_cls > 1 && gram_waves == 1 && !gram_dbg && !fuse_lin;
         if (any_ok) {
             // tracks of mixed length: every tile class in ONE launch (ba_kernels.h: k_schur_gram_any), LDS for the largest class
             const int rows_alloc = DC * F.gr_rec[(size_t)(ng - 1) * GRAM_REC + 2];
             const size_t gram_lds = ((size_t)rows_alloc * GRAM_LD + GRAM_TAIL) * sizeof(double);
             if (gram_lds > 48 * 1024) SSFM_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_schur_gram_any<DC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_lds));
             LAUNCH(h, KID_SCHUR_GRAM, (k_schur_gram_any<DC>), ng, 64, gram_lds, at.cam, at.rot, at.pts, at.focal, oxy, ng, h->gr_rec.p, h->scale_cam.p, h->scale_f.p, h->Vs.p, loss, la, rows_alloc,
-                   F.focal_free ? 1 : 0, gram_t4 ? 1 : 0, z.S_val, z.rhs, z.Udiag, z.Sfc, z.gcraw, z.det);
+                   F.focal_free ? 1 : 0, gram_t4() ? 1 : 0, z.S_val, z.rhs, z.Udiag, z.Sfc, z.gcraw, z.det);
         } else {
             GramFuse fz; fz.scale_pt = h->scale_pt.p; fz.radius = radius; fz.min_diag = O.min_lm_diagonal; fz.max_diag = O.max_lm_diagonal; fz.PS_out = h->Vs.p; fz.gp_out = h->gp.p; fz.scal = z.scal; fz.emit_skip = SSFM_LAB_KNOB("SSFM_GRAM_EMIT_SKIP", 0); fz.spec = spec;
             for (int cl = 0; cl < (DC == 6 ? 5 : 3); cl++) {              // (3-dof cameras: two row tiles at most)
