@@ -519,6 +519,47 @@ int ssfm_focal_search_graph(ssfm_ctx* ctx, int32_t n, int32_t num_edges, const i
                             const double* rel_rotations, int32_t inward, double focal_guess, int32_t num_trials, const double* focals,
                             int32_t root, double* costs, int32_t* best_trial, double* rotations_best, double* rel_rotations_best);
 
+/* ---- robust rotation initialisation for a view graph: L1 iteratively reweighted least squares on the device ------------------------
+ * ssfm_rot_l1_init: a start for ssfm_rotavg_solve that does not inherit the wrong edges of a spanning tree (Chatterjee & Govindu's robust
+ *   rotation averaging with the L1 weight, written from the mathematics; GraphOptim's initialize_rotations_gopt is not restated).  Edges as
+ *   above: R_index1 = R_e R_index0, rel_rotations column-major.  Single-GPU: a context with a communicator is refused.
+ *   Used edges: index0 != index1 and both ends reached from `root` by the walk of ssfm_view_graph_tree.  Free nodes: every reached camera but
+ *   the root.  The rotations start from the tree chain of `root` (the root and every unreached camera: identity, and they stay so).
+ *   Outer iteration k = 1 .. max_iterations:
+ *     1. per used edge e = (a, b): v_e = so3ln(R_b^T R_e R_a) (body frame), w_e = 1 / max(|v_e|, weight_floor);
+ *     2. min sum_e w_e |x_b - x_a - v_e|^2 with x_root = 0: one weighted graph Laplacian, three right-hand sides --
+ *        L_ii = sum w_e, L_ij = -sum w_e over the edges between i and j, g_i = sum_{b = i} w_e v_e - sum_{a = i} w_e v_e;
+ *     3. Jacobi-preconditioned conjugate gradients from x = 0, the three columns in lockstep with their own scalars.  Before each iteration a
+ *        column with |r|^2 <= pcg_tolerance^2 |g|^2 stops (a zero column at once); at pcg_max_iterations (0: 4 x the free node count) the
+ *        solve stops as it is and counts in pcg_solves_capped.  pcg_iterations_total adds the lockstep iterations of every solve;
+ *     4. R_i <- R_i so3exp(x_i), step = max_i |x_i|; step < step_tolerance ends with SSFM_CONVERGENCE (the update is applied first),
+ *        the iteration cap with SSFM_NO_CONVERGENCE.  step_tolerance = 0 therefore runs exactly max_iterations.
+ *   Afterwards residual_out[e] = |v_e| at the returned rotations (-1 for an unused edge; may be NULL), final_cost = sum |v_e|; initial_cost is
+ *   the same sum at the tree start.  Cutting the edges whose residual exceeds a threshold (2 degrees in the drivers) before the refinement is
+ *   what removes the outliers' bias: DESIGN.md 4, "Robust rotation initialisation".
+ *   Reproducible: no floating-point atomics, every sum is taken in a fixed order -- two calls on the same input return the same bits.
+ *   SSFM_ERR_INVALID before anything is launched: an index or the root outside [0, num_cameras), max_iterations <= 0, weight_floor <= 0,
+ *   pcg_tolerance <= 0, step_tolerance < 0, pcg_max_iterations < 0 (checked in this order: arguments, options, indices, root, then the
+ *   context).  num_edges == 0 or a root without used edges is valid: identities, 0 iterations, SSFM_CONVERGENCE.
+ *   Defaults: max_iterations 30, step_tolerance 1e-4, weight_floor 1e-3 (rad), pcg_tolerance 1e-10, pcg_max_iterations 0.
+ *   kernel_ms: device time between the first and the last launch of the call (one hipEvent pair). */
+typedef struct {
+    int32_t max_iterations;
+    double step_tolerance;
+    double weight_floor;
+    double pcg_tolerance;
+    int32_t pcg_max_iterations;
+} ssfm_rot_l1_options;
+typedef struct {
+    int32_t iterations, termination, num_free, num_edges_used, pcg_solves_capped;
+    int64_t pcg_iterations_total;
+    double initial_cost, final_cost, last_step, kernel_ms;
+} ssfm_rot_l1_summary;
+void ssfm_rot_l1_default_options(ssfm_rot_l1_options* o);
+int ssfm_rot_l1_init(ssfm_ctx* ctx, int32_t num_cameras, int32_t num_edges, const int32_t* index0, const int32_t* index1,
+                     const double* rel_rotations, int32_t root, const ssfm_rot_l1_options* opt /* NULL = defaults */,
+                     double* rotations_out /* 9 n, column-major */, double* residual_out /* E, may be NULL */, ssfm_rot_l1_summary* s);
+
 /* ---- SfM::Retriangulate (src/sfm.cpp:156-192) ------------------------------------------------------------------
  * Re-estimates EVERY point of the problem from its observations and the current cameras/focal with the per-point
  * ransac_lib::LocallyOptimizedMSAC<Point, ..., TriangulationEstimator> of the reference (src/triangulation_estimator.cpp:46-127,

@@ -75,6 +75,19 @@ class MatchOptionsC(C.Structure):
     _fields_ = [("ratio", C.c_double), ("dim", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RotL1OptionsC(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("step_tolerance", C.c_double), ("weight_floor", C.c_double), ("pcg_tolerance", C.c_double),
+                ("pcg_max_iterations", C.c_int32)]
+
+
+class RotL1SummaryC(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("termination", C.c_int32), ("num_free", C.c_int32), ("num_edges_used", C.c_int32), ("pcg_solves_capped", C.c_int32),
+                ("pcg_iterations_total", C.c_int64), ("initial_cost", C.c_double), ("final_cost", C.c_double), ("last_step", C.c_double), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 c_float_p = C.POINTER(C.c_float)
 
 
@@ -95,6 +108,7 @@ DECLARED_SYMBOLS = [
     "ssfm_match_default_options", "ssfm_match_pairs", "ssfm_match_knn_probe", "ssfm_match_last_kernel_ms",
     "ssfm_pairwise_from_features", "ssfm_pairwise_front_last_kernel_ms",
     "ssfm_triplet_filter", "ssfm_view_graph_tree", "ssfm_focal_search_graph",
+    "ssfm_rot_l1_default_options", "ssfm_rot_l1_init",
 ]
 
 
@@ -215,6 +229,10 @@ def lib():
     L.ssfm_focal_search_graph.argtypes = [vp, C.c_int32, C.c_int32, c_i32_p, c_i32_p, c_double_p, C.c_int32, C.c_double, C.c_int32, c_double_p, C.c_int32, c_double_p,
                                           c_i32_p, c_double_p, c_double_p]
     L.ssfm_focal_search_graph.restype = C.c_int
+    L.ssfm_rot_l1_default_options.argtypes = [C.POINTER(RotL1OptionsC)]; L.ssfm_rot_l1_default_options.restype = None
+    L.ssfm_rot_l1_init.argtypes = [vp, C.c_int32, C.c_int32, c_i32_p, c_i32_p, c_double_p, C.c_int32, C.POINTER(RotL1OptionsC), c_double_p, c_double_p,
+                                   C.POINTER(RotL1SummaryC)]
+    L.ssfm_rot_l1_init.restype = C.c_int
     _LIB = L
     return L
 

@@ -9,8 +9,11 @@
 // find_largest_connected_component AGAIN -- the filter can split the graph; the reference does not guard against that, this driver does -- then the rotations chained
 // along a breadth-first spanning tree (initialize_rotations_tree, in place of GraphOptim) and the same rotation averaging.  -tripletorder composed selects the product
 // order that the edge convention implies instead of the reference's (include/ssfm.h).  Without -viewgraph nothing changes.
+// -rotinit l1 (with -viewgraph; default: tree): the start is the robust one of ssfm_rot_l1_init instead of the tree chain, the matches whose residual at that start
+// exceeds -rotinitthresh degrees (default 2) are dropped, find_largest_connected_component runs once more, and refine_rotations starts from the L1 rotations of the
+// cameras that are left; rotinit.txt lists every pair with its residual.  One wrong match on a tree edge no longer rotates a whole subtree, and the gross outliers no longer bias the averaging.
 //   run_spherical_sfm -intrinsics <file: focal cx cy> -output <dir with the feature tracks> [-match | -pairwise] [-inward] [-width W -height H]
-//                     [-viewgraph [-tripletorder reference|composed]]
+//                     [-viewgraph [-tripletorder reference|composed] [-rotinit tree|l1] [-rotinitthresh DEG]]
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -21,6 +24,7 @@ using namespace sphericalsfm;
 
 int main(int argc, char** argv) {
     std::string intrinsics_path, output; bool inward = false, pairwise = false, match_mode = false, viewgraph = false; int triplet_order = SSFM_TRIPLET_ORDER_REFERENCE, width = 1920, height = 1080, mininliers = 100; double inlierthresh = 2.0;
+    bool rotinit_l1 = false; double rotinit_thresh_deg = 2.0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "-intrinsics" && i + 1 < argc) intrinsics_path = argv[++i];
@@ -39,8 +43,15 @@ int main(int argc, char** argv) {
             if (o == "composed") triplet_order = SSFM_TRIPLET_ORDER_COMPOSED; else if (o == "reference") triplet_order = SSFM_TRIPLET_ORDER_REFERENCE;
             else { std::cout << "unknown triplet order " << o << "\n"; return 2; }
         }
+        else if (a == "-rotinit" && i + 1 < argc) {
+            const std::string o = argv[++i];
+            if (o == "l1") rotinit_l1 = true; else if (o == "tree") rotinit_l1 = false;
+            else { std::cout << "unknown rotation initialisation " << o << "\n"; return 2; }
+        }
+        else if (a == "-rotinitthresh" && i + 1 < argc) rotinit_thresh_deg = std::atof(argv[++i]);
         else { std::cout << "unknown argument " << a << "\n"; return 2; }
     }
+    if (rotinit_l1 && !viewgraph) { std::cout << "-rotinit l1 needs -viewgraph\n"; return 2; }
     if (intrinsics_path.empty() || output.empty()) { std::cout << "usage: run_spherical_sfm -intrinsics <file> -output <dir> [-inward]\n"; return 2; }
     double focal, centerx, centery;
     std::ifstream intrinsicsf(intrinsics_path);
@@ -81,7 +92,23 @@ int main(int argc, char** argv) {
     }
     std::cout << "initializing rotations\n";
     std::vector<Mat3> rotations;
-    if (viewgraph) initialize_rotations_tree((int)keyframes.size(), image_matches, rotations);
+    if (viewgraph && rotinit_l1) {
+        std::vector<double> residuals; ssfm_rot_l1_summary l1;
+        const size_t edges_in = image_matches.size(), frames_in = keyframes.size();
+        initialize_rotations_l1(sfm.GetContext(), (int)keyframes.size(), image_matches, rotations, residuals, 0, &l1);
+        if (FILE* f = std::fopen((output + "/rotinit.txt").c_str(), "w")) {             // frame numbers of the pair, residual in degrees, 1 = kept
+            for (size_t e = 0; e < edges_in; e++)
+                std::fprintf(f, "%d %d %f %d\n", keyframes[image_matches[e].index0].index, keyframes[image_matches[e].index1].index, residuals[e] * 180.0 / M_PI,
+                             residuals[e] >= 0.0 && residuals[e] <= rotinit_thresh_deg * M_PI / 180.0 ? 1 : 0);
+            std::fclose(f);
+        }
+        image_matches = filter_image_matches_by_residual(image_matches, residuals, rotinit_thresh_deg * M_PI / 180.0);
+        if (image_matches.empty()) { std::cout << "error: no image match survived the residual cut\n"; return 1; }
+        find_largest_connected_component(keyframes, image_matches, rotations);          // the cut may have split the graph
+        std::printf("ROTINIT_RESULT edges_in=%zu edges_kept=%zu cameras_in=%zu cameras_kept=%zu iterations=%d cg_iterations=%lld cost_initial=%.6e cost_final=%.6e\n", edges_in,
+                    image_matches.size(), frames_in, keyframes.size(), l1.iterations, (long long)l1.pcg_iterations_total, l1.initial_cost, l1.final_cost);
+    }
+    else if (viewgraph) initialize_rotations_tree((int)keyframes.size(), image_matches, rotations);
     else initialize_rotations_sequential((int)keyframes.size(), image_matches, rotations);
 
     std::cout << "refining rotations\n";

@@ -259,6 +259,21 @@ void initialize_rotations_tree(int num_cameras, const std::vector<ImageMatch>& i
     }
 }
 
+void initialize_rotations_l1(ssfm_ctx* ctx, int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations, std::vector<double>& residuals,
+                             int root, ssfm_rot_l1_summary* summary) {
+    const int E = (int)image_matches.size();
+    std::vector<int32_t> i0(E), i1(E); std::vector<double> rel((size_t)9 * E), rot((size_t)9 * std::max(num_cameras, 0));
+    for (int e = 0; e < E; e++) { i0[e] = image_matches[e].index0; i1[e] = image_matches[e].index1; for (int k = 0; k < 9; k++) rel[9 * (size_t)e + k] = image_matches[e].R[k]; }
+    residuals.assign((size_t)E, -1.0);
+    ssfm_rot_l1_summary S;
+    if (ssfm_rot_l1_init(ctx, num_cameras, E, i0.data(), i1.data(), rel.data(), root, nullptr, rot.data(), residuals.data(), &S) != SSFM_OK) {
+        std::cout << "error: " << ssfm_last_error(ctx) << "\n"; std::exit(1);
+    }
+    rotations.resize(std::max(num_cameras, 0));
+    for (int i = 0; i < num_cameras; i++) for (int k = 0; k < 9; k++) rotations[i][k] = rot[9 * (size_t)i + k];
+    if (summary) *summary = S;
+}
+
 double refine_rotations(ssfm_ctx* ctx, int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations) {
     const int E = (int)image_matches.size();
     std::vector<int32_t> i0(E), i1(E); std::vector<double> rel((size_t)9 * E), rot((size_t)9 * num_cameras);

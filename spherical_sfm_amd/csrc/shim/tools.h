@@ -102,6 +102,18 @@ std::vector<ImageMatch> apply_triplet_filter(const std::vector<ImageMatch>& imag
 // cameras the tree does not reach keep the identity.  The robust refine_rotations that follows does the averaging.  Host code.
 void initialize_rotations_tree(int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations, int root = 0);
 
+// Robust rotation initialisation over a general view graph (ssfm_rot_l1_init: L1 iteratively reweighted least squares from the tree chain of `root`, on the device):
+// rotations as initialize_rotations_tree returns them, residuals[e] = |so3ln(R_b^T R_e R_a)| in radians at those rotations (-1 for a match that is not used: a self
+// loop, or cameras `root` does not reach).  Default options.  Exits on an error of the library, like refine_rotations.
+void initialize_rotations_l1(ssfm_ctx* ctx, int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations, std::vector<double>& residuals,
+                             int root = 0, ssfm_rot_l1_summary* summary = nullptr);
+// The matches whose residual lies in [0, thresh_rad], in list order (host code, tools_host.cpp).  Together with the start above this is what keeps gross outliers
+// out of refine_rotations: DESIGN.md 4, "Robust rotation initialisation".
+std::vector<ImageMatch> filter_image_matches_by_residual(const std::vector<ImageMatch>& image_matches, const std::vector<double>& residuals, double thresh_rad);
+// find_largest_connected_component with per-camera rotations carried along: kept cameras keep their rotation, re-gauged so that the new camera 0 has the identity
+// (R_i <- R_i R_0^T leaves every R_b R_a^T as it is).  Host code.
+void find_largest_connected_component(std::vector<Keyframe>& keyframes, std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations);
+
 // The reference seeds std::mt19937 from std::random_device and draws inside an OpenMP loop; here the draw is sequential from
 // `seed` (deterministic), everything after it follows the reference: costs of all trials in one GPU launch, first minimum,
 // the initial rotations at the best focal, then the joint rotation + focal refinement.  sequential = true chains the matches (k-1, k)

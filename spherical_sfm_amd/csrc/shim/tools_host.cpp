@@ -134,4 +134,34 @@ void find_largest_connected_component(std::vector<Keyframe>& keyframes, std::vec
     keyframes.swap(kept); image_matches.swap(kept_matches);
 }
 
+std::vector<ImageMatch> filter_image_matches_by_residual(const std::vector<ImageMatch>& image_matches, const std::vector<double>& residuals, double thresh_rad) {
+    std::vector<ImageMatch> kept;
+    for (size_t e = 0; e < image_matches.size() && e < residuals.size(); e++)
+        if (residuals[e] >= 0.0 && residuals[e] <= thresh_rad) kept.push_back(image_matches[e]);
+    return kept;
+}
+
+void find_largest_connected_component(std::vector<Keyframe>& keyframes, std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations) {
+    // Keyframe::index is the one field the component pass carries through untouched: lend it the position for the duration of the call
+    std::vector<int> index(keyframes.size());
+    for (size_t i = 0; i < keyframes.size(); i++) { index[i] = keyframes[i].index; keyframes[i].index = (int)i; }
+    find_largest_connected_component(keyframes, image_matches);
+    const Mat3 I = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    std::vector<Mat3> kept(keyframes.size(), I);
+    for (size_t k = 0; k < keyframes.size(); k++) {
+        const size_t pos = (size_t)keyframes[k].index;
+        keyframes[k].index = index[pos];
+        if (pos < rotations.size()) kept[k] = rotations[pos];
+    }
+    if (!kept.empty()) {
+        const Mat3 R0 = kept[0];
+        for (Mat3& R : kept) {                                                            // R <- R R0^T, column-major
+            Mat3 Rn;
+            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) { double s = 0; for (int q = 0; q < 3; q++) s += R[r + 3 * q] * R0[c + 3 * q]; Rn[r + 3 * c] = s; }
+            R = Rn;
+        }
+    }
+    rotations.swap(kept);
+}
+
 }  // namespace sphericalsfm

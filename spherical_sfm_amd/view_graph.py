@@ -54,6 +54,27 @@ def initialize_rotations_tree(num_cameras, index0, index1, rel_rotations, root=0
     return rot
 
 
+def initialize_rotations_l1(ctx, num_cameras, index0, index1, rel_rotations, root=0, **options):
+    """Robust start over any view graph (ssfm_rot_l1_init: L1 iteratively reweighted least squares from the tree chain of `root`, conjugate gradients on the device)
+    -> (rotations (n,3,3), residuals (E,) = |so3ln(R_b^T R_e R_a)| in radians at those rotations, -1 for an edge that is not used, summary dict).
+    options: max_iterations, step_tolerance, weight_floor, pcg_tolerance, pcg_max_iterations (include/ssfm.h states the defaults).  Dropping the edges whose
+    residual exceeds a threshold before optimize_rotations is what removes the outliers' bias."""
+    L = _lib.lib()
+    n = int(num_cameras)
+    i0, i1, rel = _edges(index0, index1, rel_rotations) if len(index0) else (np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0))
+    E = len(i0)
+    o = _lib.RotL1OptionsC(); L.ssfm_rot_l1_default_options(C.byref(o))
+    for k, v in options.items():
+        if k not in dict(o._fields_):
+            raise TypeError(f"initialize_rotations_l1: unknown option {k!r}")
+        setattr(o, k, v)
+    rot = np.zeros(9 * max(n, 1)); res = np.zeros(max(E, 1)); s = _lib.RotL1SummaryC()
+    p = ctx._p if ctx is not None else None
+    _lib.check(L.ssfm_rot_l1_init(p, n, E, i0.ctypes.data_as(c_i32_p), i1.ctypes.data_as(c_i32_p), rel.ctypes.data_as(c_double_p), int(root), C.byref(o),
+                                  rot.ctypes.data_as(c_double_p), res.ctypes.data_as(c_double_p), C.byref(s)), p)
+    return np.transpose(rot[:9 * n].reshape(-1, 3, 3), (0, 2, 1)).copy(), res[:E].copy(), s.as_dict()
+
+
 def focal_search_graph(ctx, num_cameras, index0, index1, rel_rotations, focal_guess, focals, inward=False, root=0, return_matches=False):
     """rotavg.focal_search with the rotations of every trial chained along the spanning tree (ssfm_focal_search_graph) -> the same tuple."""
     i0, i1, rel = _edges(index0, index1, rel_rotations)
