@@ -401,7 +401,27 @@ int ssfm_pairwise_from_features(ssfm_ctx* ctx, int32_t num_frames, const int32_t
                                 const ssfm_ransac_options* ransac_opt, double squared_inlier_threshold, int64_t pair_capacity, int64_t inlier_capacity,
                                 int64_t* needed, int32_t* accepted_pair, double* R, int32_t* num_inliers, int32_t* inl_ptr, int32_t* inl_idx0,
                                 int32_t* inl_idx1, int32_t* match_count, int32_t* num_inliers_all, uint32_t* stats);
-/* Device time of the kernels of this context's last ssfm_pairwise_from_features call: the brackets of ssfm_match_last_kernel_ms and
+/* The same front end with general relative pose in the third place: match_exhaustive + estimate_pairwise_five_point (:575-600, :433-573), what
+ * run_spherical_sfm_uncalib -match -fivepoint runs.  DEFINED by composition -- the outputs are, bit for bit, those of
+ *   1. ssfm_match_pairs on all pairs;
+ *   2. the candidates: pairs with count >= min_num_inliers and count > 0 (:475), in pair order;
+ *   3. ssfm_ransac5_batch_indexed on exactly that candidate list (candidate k gets random stream k);
+ *   4. the candidates with num_inliers > min_num_inliers (:534) and a non-empty inlier list; of these the INLIER matches only, ascending train index.
+ * The match kernels and the five-point LO-MSAC kernel run unchanged with the launch parameters of the two public calls, the slab plans are made from the
+ * same counts, and SSFM_MATCH_SLAB_PAIRS, SSFM_RANSAC_SLAB_PAIRS, SSFM_RANSAC_SLAB_RAYS and SSFM_RANSAC5_FORCE_GLOBAL act as they do there.  The options
+ * are the struct of ssfm_ransac_batch; the fields used and the fields IGNORED are those listed at ssfm_ransac5_batch (reference-trace mode only).
+ * Arguments, capacity protocol, optional per-pair outputs and refusals are those of ssfm_pairwise_from_features; in addition
+ *   t [3 * pair_capacity]   the unit translation of every accepted pair (x1 = R x0 + t); required;
+ *   E [9 * pair_capacity]   column-major, the matrix ssfm_ransac5_batch_indexed returns for the pair, with that call's sign; may be NULL.
+ * Per accepted pair 24 bytes (t) come back beside what the spherical call brings back, and 72 bytes more when E is asked for; E, the scores and the masks
+ * of the other candidates stay on the device.  Messages are prefixed ssfm_pairwise5_from_features.  Single-GPU: a context with a communicator is
+ * refused (the sharded calls have no five-point form). */
+int ssfm_pairwise5_from_features(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, const float* descs, const double* feat_rays,
+                                 int32_t num_pairs, const int32_t* pair_frame0, const int32_t* pair_frame1, const ssfm_match_options* match_opt,
+                                 const ssfm_ransac_options* ransac_opt, double squared_inlier_threshold, int64_t pair_capacity, int64_t inlier_capacity,
+                                 int64_t* needed, int32_t* accepted_pair, double* R, double* t, double* E /* may be NULL */, int32_t* num_inliers,
+                                 int32_t* inl_ptr, int32_t* inl_idx0, int32_t* inl_idx1, int32_t* match_count, int32_t* num_inliers_all, uint32_t* stats);
+/* Device time of the kernels of this context's last ssfm_pairwise_from_features or ssfm_pairwise5_from_features call (whichever came last): the brackets of ssfm_match_last_kernel_ms and
  * ssfm_ransac_last_kernel_ms, the latter with the hand-over kernels inside.  NOT included: the device-to-device copies that append every match slab's lists
  * to the call's list (8 bytes per match, once; copied again when the list has to grow), which run between the two brackets. */
 int ssfm_pairwise_front_last_kernel_ms(ssfm_ctx* ctx, double* ms);

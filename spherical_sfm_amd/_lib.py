@@ -106,7 +106,7 @@ DECLARED_SYMBOLS = [
     "ssfm_estimator_create", "ssfm_estimator_destroy", "ssfm_estimator_minimal_solver", "ssfm_estimator_non_minimal_solver",
     "ssfm_estimator_evaluate_model", "ssfm_estimator_least_squares", "ssfm_estimator_decompose",
     "ssfm_match_default_options", "ssfm_match_pairs", "ssfm_match_knn_probe", "ssfm_match_last_kernel_ms",
-    "ssfm_pairwise_from_features", "ssfm_pairwise_front_last_kernel_ms",
+    "ssfm_pairwise_from_features", "ssfm_pairwise5_from_features", "ssfm_pairwise_front_last_kernel_ms",
     "ssfm_triplet_filter", "ssfm_view_graph_tree", "ssfm_focal_search_graph",
     "ssfm_rot_l1_default_options", "ssfm_rot_l1_init",
 ]
@@ -221,6 +221,10 @@ def lib():
     L.ssfm_pairwise_from_features.argtypes = [vp, C.c_int32, c_i32_p, c_float_p, c_double_p, C.c_int32, c_i32_p, c_i32_p, C.POINTER(MatchOptionsC), C.POINTER(RansacOptionsC),
                                               C.c_double, C.c_int64, C.c_int64, c_i64_p, c_i32_p, c_double_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_u32_p]
     L.ssfm_pairwise_from_features.restype = C.c_int
+    L.ssfm_pairwise5_from_features.argtypes = [vp, C.c_int32, c_i32_p, c_float_p, c_double_p, C.c_int32, c_i32_p, c_i32_p, C.POINTER(MatchOptionsC), C.POINTER(RansacOptionsC),
+                                               C.c_double, C.c_int64, C.c_int64, c_i64_p, c_i32_p, c_double_p, c_double_p, c_double_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p,
+                                               c_i32_p, c_u32_p]
+    L.ssfm_pairwise5_from_features.restype = C.c_int
     L.ssfm_pairwise_front_last_kernel_ms.argtypes = [vp, c_double_p]; L.ssfm_pairwise_front_last_kernel_ms.restype = C.c_int
     L.ssfm_triplet_filter.argtypes = [vp, C.c_int32, C.c_int32, c_i32_p, c_i32_p, c_double_p, C.c_double, C.c_int32, c_u8_p, c_i64_p, C.c_int64, c_i32_p, c_double_p]
     L.ssfm_triplet_filter.restype = C.c_int

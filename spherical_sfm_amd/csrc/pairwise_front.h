@@ -1,5 +1,5 @@
-// spherical_sfm_amd -- what match.hip, ransac.hip and pairwise_front.hip share so that ssfm_pairwise_from_features can run the existing
-// matching and LO-MSAC kernels with the match lists staying on the device.
+// spherical_sfm_amd -- what match.hip, ransac.hip and pairwise_front.hip share so that ssfm_pairwise_from_features and ssfm_pairwise5_from_features can run
+// the existing matching and LO-MSAC kernels with the match lists staying on the device.
 #pragma once
 #include <functional>
 #include "ssfm_ctx.h"
@@ -35,17 +35,21 @@ int match_slabs(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, cons
 
 // ---- ransac.hip -----------------------------------------------------------------------------------------------------------------
 // ransac_batch_impl on match lists that are already on the device.  The slab plan, the kernels and their launch parameters are those of
-// ssfm_ransac_batch_indexed; the hooks replace the host staging of the lists (stage / gather) and the copy of the inlier mask (lists / collect).
-// `slot` is the double-buffer slot (0 / 1) of the slab, p0 / np its pairs; d_ptr is the slab-local CSR of its correspondences.
+// ssfm_ransac_batch_indexed -- with five = true those of ssfm_ransac5_batch_indexed (k_lomsac5_trace; the options go through ransac5_options and `who` names
+// the entry point in the messages); the hooks replace the host staging of the lists (stage / gather) and the copy of the inlier mask (lists / collect).
+// `slot` is the double-buffer slot (0 / 1) of the slab, p0 / np its pairs; d_ptr is the slab-local CSR of its correspondences.  d_R / d_E [9 np] are
+// row-major, d_t [3 np]; d_E and d_t are null in spherical mode.
 struct RansacDeviceLists {
     virtual int prepare(int nslot, int cap_pairs, size_t cap_rays) = 0;                        // per-slot buffers
     virtual int stage(hipStream_t up, int slot, int p0, int np) = 0;                           // the slab's per-pair source table, on the upload stream
     virtual int gather(hipStream_t st, int slot, int np, const int* d_ptr, double* d_u, double* d_v) = 0;
-    virtual int lists(hipStream_t st, int slot, int np, const int* d_ptr, const unsigned char* d_mask, const int* d_nin, const double* d_R) = 0;   // after the RANSAC kernels
+    virtual int lists(hipStream_t st, int slot, int np, const int* d_ptr, const unsigned char* d_mask, const int* d_nin, const double* d_R, const double* d_E,
+                      const double* d_t) = 0;                                                  // after the RANSAC kernels
     virtual int collect(hipStream_t cp, int slot, int p0, int np) = 0;                         // the slab has finished: copy back what was accepted
     virtual ~RansacDeviceLists() {}
 };
 int ransac_on_device_lists(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, int32_t num_pairs, const int32_t* pair_frame0, const int32_t* pair_frame1,
-                           const int32_t* pair_ptr, double sq_thresh, const ssfm_ransac_options& O, RansacDeviceLists* hooks, int32_t* num_inliers, uint32_t* stats);
+                           const int32_t* pair_ptr, double sq_thresh, const ssfm_ransac_options& O, RansacDeviceLists* hooks, int32_t* num_inliers, uint32_t* stats,
+                           bool five = false, const char* who = nullptr);
 
 }  // namespace ssfm

@@ -1,16 +1,19 @@
 // spherical_sfm_amd -- the pairwise front end in one call: match_exhaustive + estimate_pairwise (reference examples/spherical_sfm_tools.cpp:575-600 and
-// :309-420) for a caller-given pair list, with the match lists staying on the device between the two stages.
+// :309-420) or + estimate_pairwise_five_point (:433-573) for a caller-given pair list, with the match lists staying on the device between the two stages.
 //
 // ssfm_pairwise_from_features is DEFINED as the composition
 //   ssfm_match_pairs -> candidates (count >= min_num_inliers, count > 0) -> ssfm_ransac_batch_indexed on the candidates -> num_inliers > min_num_inliers
-// and runs exactly those kernels with those launch parameters (match.hip: match_slabs, ransac.hip: ransac_on_device_lists -- the slab plan is made from the
-// same counts).  What is new here is the hand-over around them:
+// and ssfm_pairwise5_from_features as the same with ssfm_ransac5_batch_indexed in the third place.  Both run exactly those kernels with those launch
+// parameters (match.hip: match_slabs, ransac.hip: ransac_on_device_lists -- the slab plan is made from the same counts).  What is new here is the hand-over
+// around them:
 //   k_front_gather    k_gather_rays' job from the device-resident lists of the candidate pairs (every list index is range-checked before it addresses a ray)
 //   k_front_count     per candidate: inliers in its mask, acceptance flag
 //   k_front_scan      exclusive scans over the slab's pairs (one workgroup): position among the accepted pairs, start of the inlier list
-//   k_front_compact   (idx0, idx1) of the inliers of accepted pairs, in list order (= ascending train index); R (column-major) and counts per accepted pair
+//   k_front_compact   (idx0, idx1) of the inliers of accepted pairs, in list order (= ascending train index); R (column-major) and counts per accepted pair;
+//                     the five-point instantiation also t and E (column-major) per accepted pair
 // Per pair 4 bytes of counts come back after matching and 8 bytes of diagnostics after RANSAC; the lists and the byte mask never leave the device, only the
-// accepted pairs' R / counts / inlier lists do.  No atomics, no inter-workgroup waiting: the same bits every run.
+// accepted pairs' R / counts / inlier lists do (five-point: + 24 bytes of t, + 72 bytes of E when it is asked for).  No atomics, no inter-workgroup
+// waiting: the same bits every run.
 #include <algorithm>
 #include <cstring>
 #include <limits>
@@ -69,16 +72,22 @@ k_front_scan(int np, const int* __restrict__ cnt, const int* __restrict__ acc, i
 }
 
 // meta[3 a] = {slab-local pair, num_inliers, start of the inlier list} of accepted pair a; Racc[9 a]: its rotation, column-major
-static __global__ void __launch_bounds__(256)
+// FIVE: also Eacc[9 a], its essential matrix, column-major, and Tacc[3 a], its translation (one wave each for R, E and t: three independent loads)
+template <bool FIVE> static __global__ void __launch_bounds__(256)
 k_front_compact(const int* __restrict__ ptr, const unsigned char* __restrict__ mask, const FrontPair* __restrict__ info, const int* __restrict__ idx0,
                 const int* __restrict__ idx1, int list_len, const int* __restrict__ optr, const int* __restrict__ apos, const int* __restrict__ acc,
-                const int* __restrict__ nin, const double* __restrict__ R, int out_cap, int* __restrict__ o0, int* __restrict__ o1, double* __restrict__ Racc,
-                int* __restrict__ meta) {
+                const int* __restrict__ nin, const double* __restrict__ R, const double* __restrict__ E, const double* __restrict__ T, int out_cap,
+                int* __restrict__ o0, int* __restrict__ o1, double* __restrict__ Racc, double* __restrict__ Eacc, double* __restrict__ Tacc, int* __restrict__ meta) {
     const int p = blockIdx.x;
     if (!acc[p]) return;                                             // (uniform over the workgroup)
     const int r0 = ptr[p], n = ptr[p + 1] - r0, a = apos[p], src = info[p].src;
     int base = optr[p];
     if (threadIdx.x < 9) Racc[9 * (size_t)a + (threadIdx.x / 3) + 3 * (threadIdx.x % 3)] = R[9 * (size_t)p + threadIdx.x];      // row-major -> column-major
+    if constexpr (FIVE) {
+        const int q = (int)threadIdx.x - 64, c = (int)threadIdx.x - 128;
+        if (q >= 0 && q < 9) Eacc[9 * (size_t)a + (q / 3) + 3 * (q % 3)] = E[9 * (size_t)p + q];
+        if (c >= 0 && c < 3) Tacc[3 * (size_t)a + c] = T[3 * (size_t)p + c];
+    }
     if (threadIdx.x == 0) { meta[3 * a] = p; meta[3 * a + 1] = nin[p]; meta[3 * a + 2] = base; }
     for (int b = 0; b < n; b += 256) {
         const int i = b + threadIdx.x;
@@ -93,16 +102,16 @@ k_front_compact(const int* __restrict__ ptr, const unsigned char* __restrict__ m
 namespace {
 
 struct FrontHooks : RansacDeviceLists {
-    ssfm_ctx* ctx = nullptr;
+    ssfm_ctx* ctx = nullptr; const char* who = ""; bool five = false;
     // the call's match lists on the device and the candidate table on the host
     const int* d_idx0 = nullptr; const int* d_idx1 = nullptr; int list_len = 0; const double* d_frays = nullptr;
     const int32_t* feat_ptr = nullptr; const int32_t* cf0 = nullptr; const int32_t* cf1 = nullptr; const int32_t* csrc = nullptr; const int32_t* cand = nullptr;
     int min_num_inliers = 0;
     // the caller's outputs
     int64_t pair_capacity = 0, inlier_capacity = 0;
-    int32_t* accepted_pair = nullptr; double* R = nullptr; int32_t* num_inliers = nullptr; int32_t* inl_ptr = nullptr; int32_t* inl_idx0 = nullptr; int32_t* inl_idx1 = nullptr;
+    int32_t* accepted_pair = nullptr; double* R = nullptr; double* t = nullptr; double* E = nullptr; int32_t* num_inliers = nullptr; int32_t* inl_ptr = nullptr; int32_t* inl_idx0 = nullptr; int32_t* inl_idx1 = nullptr;
     int64_t acc_run = 0, inl_run = 0; bool overflow = false;
-    struct Slot { DevBuf<FrontPair> info; DevBuf<int> cnt, acc, optr, apos, tot, o0, o1, meta; DevBuf<double> Racc; FrontPair* h_info = nullptr; int* h_tot = nullptr; } slot[2];
+    struct Slot { DevBuf<FrontPair> info; DevBuf<int> cnt, acc, optr, apos, tot, o0, o1, meta; DevBuf<double> Racc, Eacc, Tacc; FrontPair* h_info = nullptr; int* h_tot = nullptr; } slot[2];
     int cap_pairs = 0; size_t cap_rays = 0;
     std::vector<int> hmeta;
 
@@ -114,6 +123,7 @@ struct FrontHooks : RansacDeviceLists {
             SSFM_HIP_CHECK(ctx, s.optr.alloc((size_t)cap_pairs + 1)); SSFM_HIP_CHECK(ctx, s.apos.alloc((size_t)cap_pairs + 1)); SSFM_HIP_CHECK(ctx, s.tot.alloc(3));
             SSFM_HIP_CHECK(ctx, s.o0.alloc(cap_rays)); SSFM_HIP_CHECK(ctx, s.o1.alloc(cap_rays)); SSFM_HIP_CHECK(ctx, s.meta.alloc((size_t)3 * cap_pairs));
             SSFM_HIP_CHECK(ctx, s.Racc.alloc((size_t)9 * cap_pairs));
+            if (five) { SSFM_HIP_CHECK(ctx, s.Eacc.alloc((size_t)9 * cap_pairs)); SSFM_HIP_CHECK(ctx, s.Tacc.alloc((size_t)3 * cap_pairs)); }
             SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_info, (size_t)cap_pairs * sizeof(FrontPair), hipHostMallocDefault));
             SSFM_HIP_CHECK(ctx, hipHostMalloc((void**)&s.h_tot, 3 * sizeof(int), hipHostMallocDefault));
         }
@@ -136,13 +146,17 @@ struct FrontHooks : RansacDeviceLists {
         SSFM_HIP_CHECK(ctx, hipGetLastError());
         return SSFM_OK;
     }
-    int lists(hipStream_t st, int b, int np, const int* d_ptr, const unsigned char* d_mask, const int* d_nin, const double* d_R) override {
+    int lists(hipStream_t st, int b, int np, const int* d_ptr, const unsigned char* d_mask, const int* d_nin, const double* d_R, const double* d_E,
+              const double* d_t) override {
         Slot& s = slot[b];
         if (np > 0) {
             hipLaunchKernelGGL(k_front_count, dim3(np), dim3(256), 0, st, d_ptr, d_mask, d_nin, min_num_inliers, s.cnt.p, s.acc.p);
             hipLaunchKernelGGL(k_front_scan, dim3(1), dim3(256), 0, st, np, s.cnt.p, s.acc.p, s.optr.p, s.apos.p, s.tot.p);
-            hipLaunchKernelGGL(k_front_compact, dim3(np), dim3(256), 0, st, d_ptr, d_mask, s.info.p, d_idx0, d_idx1, list_len, s.optr.p, s.apos.p, s.acc.p, d_nin, d_R,
-                               (int)std::min<size_t>(cap_rays, (size_t)std::numeric_limits<int>::max()), s.o0.p, s.o1.p, s.Racc.p, s.meta.p);
+            const int out_cap = (int)std::min<size_t>(cap_rays, (size_t)std::numeric_limits<int>::max());
+            if (five) hipLaunchKernelGGL(k_front_compact<true>, dim3(np), dim3(256), 0, st, d_ptr, d_mask, s.info.p, d_idx0, d_idx1, list_len, s.optr.p, s.apos.p, s.acc.p, d_nin,
+                                         d_R, d_E, d_t, out_cap, s.o0.p, s.o1.p, s.Racc.p, s.Eacc.p, s.Tacc.p, s.meta.p);
+            else hipLaunchKernelGGL(k_front_compact<false>, dim3(np), dim3(256), 0, st, d_ptr, d_mask, s.info.p, d_idx0, d_idx1, list_len, s.optr.p, s.apos.p, s.acc.p, d_nin,
+                                    d_R, (const double*)nullptr, (const double*)nullptr, out_cap, s.o0.p, s.o1.p, s.Racc.p, (double*)nullptr, (double*)nullptr, s.meta.p);
             SSFM_HIP_CHECK(ctx, hipGetLastError());
         }
         SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_tot, s.tot.p, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -152,11 +166,13 @@ struct FrontHooks : RansacDeviceLists {
         Slot& s = slot[b];
         (void)np;
         const int na = s.h_tot[0], ni = s.h_tot[1];
-        if (s.h_tot[2]) return fail(ctx, SSFM_ERR_INVALID, "ssfm_pairwise_from_features: a match index on the device is out of range");
+        if (s.h_tot[2]) return fail(ctx, SSFM_ERR_INVALID, std::string(who) + ": a match index on the device is out of range");
         if (!overflow && acc_run + na <= pair_capacity && inl_run + ni <= inlier_capacity) {
             if (na) {
                 SSFM_HIP_CHECK(ctx, hipMemcpyAsync(hmeta.data(), s.meta.p, (size_t)3 * na * sizeof(int), hipMemcpyDeviceToHost, cp));
                 SSFM_HIP_CHECK(ctx, hipMemcpyAsync(R + 9 * (size_t)acc_run, s.Racc.p, (size_t)9 * na * sizeof(double), hipMemcpyDeviceToHost, cp));
+                if (five) SSFM_HIP_CHECK(ctx, hipMemcpyAsync(t + 3 * (size_t)acc_run, s.Tacc.p, (size_t)3 * na * sizeof(double), hipMemcpyDeviceToHost, cp));
+                if (five && E) SSFM_HIP_CHECK(ctx, hipMemcpyAsync(E + 9 * (size_t)acc_run, s.Eacc.p, (size_t)9 * na * sizeof(double), hipMemcpyDeviceToHost, cp));
                 if (ni) {
                     SSFM_HIP_CHECK(ctx, hipMemcpyAsync(inl_idx0 + inl_run, s.o0.p, (size_t)ni * sizeof(int), hipMemcpyDeviceToHost, cp));
                     SSFM_HIP_CHECK(ctx, hipMemcpyAsync(inl_idx1 + inl_run, s.o1.p, (size_t)ni * sizeof(int), hipMemcpyDeviceToHost, cp));
@@ -174,7 +190,7 @@ struct FrontHooks : RansacDeviceLists {
     void release() {
         for (int b = 0; b < 2; b++) {
             Slot& s = slot[b];
-            s.info.free(); s.cnt.free(); s.acc.free(); s.optr.free(); s.apos.free(); s.tot.free(); s.o0.free(); s.o1.free(); s.meta.free(); s.Racc.free();
+            s.info.free(); s.cnt.free(); s.acc.free(); s.optr.free(); s.apos.free(); s.tot.free(); s.o0.free(); s.o1.free(); s.meta.free(); s.Racc.free(); s.Eacc.free(); s.Tacc.free();
             if (s.h_info) (void)hipHostFree(s.h_info); if (s.h_tot) (void)hipHostFree(s.h_tot);
             s.h_info = nullptr; s.h_tot = nullptr;
         }
@@ -192,15 +208,14 @@ extern "C" int ssfm_pairwise_front_last_kernel_ms(ssfm_ctx* ctx, double* ms) {
     return SSFM_OK;
 }
 
-extern "C" int ssfm_pairwise_from_features(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, const float* descs, const double* feat_rays, int32_t num_pairs,
-                                           const int32_t* pair_frame0, const int32_t* pair_frame1, const ssfm_match_options* match_opt,
-                                           const ssfm_ransac_options* ransac_opt, double squared_inlier_threshold, int64_t pair_capacity, int64_t inlier_capacity,
-                                           int64_t* needed, int32_t* accepted_pair, double* R, int32_t* num_inliers, int32_t* inl_ptr, int32_t* inl_idx0,
-                                           int32_t* inl_idx1, int32_t* match_count, int32_t* num_inliers_all, uint32_t* stats) {
+// both entry points; five: the five-point estimator, t required, E optional (spherical: both null)
+static int front_impl(const char* who, bool five, ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, const float* descs, const double* feat_rays, int32_t num_pairs,
+                      const int32_t* pair_frame0, const int32_t* pair_frame1, const ssfm_match_options* match_opt, const ssfm_ransac_options* ransac_opt,
+                      double squared_inlier_threshold, int64_t pair_capacity, int64_t inlier_capacity, int64_t* needed, int32_t* accepted_pair, double* R, double* t, double* E,
+                      int32_t* num_inliers, int32_t* inl_ptr, int32_t* inl_idx0, int32_t* inl_idx1, int32_t* match_count, int32_t* num_inliers_all, uint32_t* stats) {
     // the argument checks come before anything touches a device (and before the context is looked at: without one the message goes to ssfm_last_error(NULL))
-    const char* who = "ssfm_pairwise_from_features";
-    if (!needed || !accepted_pair || !R || !num_inliers || !inl_ptr || !inl_idx0 || !inl_idx1 || pair_capacity < 0 || inlier_capacity < 0)
-        return fail(ctx, SSFM_ERR_INVALID, std::string(who) + ": needed, accepted_pair, R, num_inliers, inl_ptr, inl_idx0 and inl_idx1 are required, the capacities are >= 0");
+    if (!needed || !accepted_pair || !R || (five && !t) || !num_inliers || !inl_ptr || !inl_idx0 || !inl_idx1 || pair_capacity < 0 || inlier_capacity < 0)
+        return fail(ctx, SSFM_ERR_INVALID, std::string(who) + ": needed, accepted_pair, R, " + (five ? "t, " : "") + "num_inliers, inl_ptr, inl_idx0 and inl_idx1 are required, the capacities are >= 0");
     ssfm_match_options MO; ssfm_match_default_options(&MO);
     if (num_frames == 0 && num_pairs > 0) return fail(ctx, SSFM_ERR_INVALID, std::string(who) + ": frame index out of range");
     if (num_frames != 0 || num_pairs != 0) {
@@ -208,7 +223,7 @@ extern "C" int ssfm_pairwise_from_features(ssfm_ctx* ctx, int32_t num_frames, co
         if (feat_ptr[num_frames] && !feat_rays) return fail(ctx, SSFM_ERR_INVALID, std::string(who) + ": feat_rays is null");
     }
     if (!ctx) return fail(nullptr, SSFM_ERR_INVALID, std::string(who) + ": ctx is null");
-    if (ctx->collective) return fail(ctx, SSFM_ERR_INVALID, std::string(who) + ": the context carries a communicator; this call is single-GPU (multi-GPU: ssfm_match_pairs + ssfm_ransac_batch_indexed_sharded)");
+    if (ctx->collective) return fail(ctx, SSFM_ERR_INVALID, std::string(who) + ": the context carries a communicator; this call is single-GPU" + (five ? "" : " (multi-GPU: ssfm_match_pairs + ssfm_ransac_batch_indexed_sharded)"));
     ssfm_ransac_options RO; if (ransac_opt) RO = *ransac_opt; else ssfm_ransac_default_options(&RO);
     needed[0] = needed[1] = 0; inl_ptr[0] = 0;
     ctx->front_kernel_ms = 0.0;
@@ -263,12 +278,12 @@ extern "C" int ssfm_pairwise_from_features(ssfm_ctx* ctx, int32_t num_frames, co
         SSFM_HIP_CHECK(ctx, frays.alloc(std::max<size_t>(1, 3 * nf)));
         if (nf) SSFM_HIP_CHECK(ctx, hipMemcpyAsync(frays.p, feat_rays, 3 * nf * sizeof(double), hipMemcpyHostToDevice, st));
         SSFM_HIP_CHECK(ctx, hipStreamSynchronize(st));               // (the slabs' tables go up on another stream)
-        H.ctx = ctx; H.d_idx0 = all0.p; H.d_idx1 = all1.p; H.list_len = (int)used; H.d_frays = frays.p;
+        H.ctx = ctx; H.who = who; H.five = five; H.t = t; H.E = E; H.d_idx0 = all0.p; H.d_idx1 = all1.p; H.list_len = (int)used; H.d_frays = frays.p;
         H.feat_ptr = feat_ptr; H.cf0 = cf0.data(); H.cf1 = cf1.data(); H.csrc = csrc.data(); H.cand = cand.data(); H.min_num_inliers = RO.min_num_inliers;
         H.pair_capacity = pair_capacity; H.inlier_capacity = inlier_capacity;
         H.accepted_pair = accepted_pair; H.R = R; H.num_inliers = num_inliers; H.inl_ptr = inl_ptr; H.inl_idx0 = inl_idx0; H.inl_idx1 = inl_idx1;
         std::vector<int32_t> nin((size_t)K, 0); std::vector<uint32_t> cst((size_t)2 * K, 0);
-        rc = ransac_on_device_lists(ctx, num_frames, feat_ptr, K, cf0.data(), cf1.data(), cptr.data(), squared_inlier_threshold, RO, &H, nin.data(), cst.data());
+        rc = ransac_on_device_lists(ctx, num_frames, feat_ptr, K, cf0.data(), cf1.data(), cptr.data(), squared_inlier_threshold, RO, &H, nin.data(), cst.data(), five, who);
         if (rc) return rc;
         ctx->front_kernel_ms += ctx->ransac_kernel_ms;
         for (int k = 0; k < K; k++) {
@@ -284,4 +299,26 @@ extern "C" int ssfm_pairwise_from_features(ssfm_ctx* ctx, int32_t num_frames, co
     (void)hipStreamSynchronize(st);
     H.release(); all0.free(); all1.free(); old0.free(); old1.free(); frays.free();
     return rc;
+}
+
+extern "C" int ssfm_pairwise_from_features(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, const float* descs, const double* feat_rays, int32_t num_pairs,
+                                           const int32_t* pair_frame0, const int32_t* pair_frame1, const ssfm_match_options* match_opt,
+                                           const ssfm_ransac_options* ransac_opt, double squared_inlier_threshold, int64_t pair_capacity, int64_t inlier_capacity,
+                                           int64_t* needed, int32_t* accepted_pair, double* R, int32_t* num_inliers, int32_t* inl_ptr, int32_t* inl_idx0,
+                                           int32_t* inl_idx1, int32_t* match_count, int32_t* num_inliers_all, uint32_t* stats) {
+    return front_impl("ssfm_pairwise_from_features", false, ctx, num_frames, feat_ptr, descs, feat_rays, num_pairs, pair_frame0, pair_frame1, match_opt, ransac_opt,
+                      squared_inlier_threshold, pair_capacity, inlier_capacity, needed, accepted_pair, R, nullptr, nullptr, num_inliers, inl_ptr, inl_idx0, inl_idx1, match_count,
+                      num_inliers_all, stats);
+}
+
+// the same with ssfm_ransac5_batch_indexed as the estimator (the options go through ransac5_options inside ransac_on_device_lists; min_num_inliers, which also
+// selects the candidates here, is not among the fields it overrides)
+extern "C" int ssfm_pairwise5_from_features(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, const float* descs, const double* feat_rays, int32_t num_pairs,
+                                            const int32_t* pair_frame0, const int32_t* pair_frame1, const ssfm_match_options* match_opt,
+                                            const ssfm_ransac_options* ransac_opt, double squared_inlier_threshold, int64_t pair_capacity, int64_t inlier_capacity,
+                                            int64_t* needed, int32_t* accepted_pair, double* R, double* t, double* E, int32_t* num_inliers, int32_t* inl_ptr,
+                                            int32_t* inl_idx0, int32_t* inl_idx1, int32_t* match_count, int32_t* num_inliers_all, uint32_t* stats) {
+    return front_impl("ssfm_pairwise5_from_features", true, ctx, num_frames, feat_ptr, descs, feat_rays, num_pairs, pair_frame0, pair_frame1, match_opt, ransac_opt,
+                      squared_inlier_threshold, pair_capacity, inlier_capacity, needed, accepted_pair, R, t, E, num_inliers, inl_ptr, inl_idx0, inl_idx1, match_count,
+                      num_inliers_all, stats);
 }

@@ -223,7 +223,7 @@ int lomsac5_launch(ssfm_ctx* ctx, hipStream_t st, int num_pairs, int max_n, cons
 // than one allocation should hold and far more than one copy should block on): slab k+1 is packed into the second pinned buffer and copied
 // on the context's copy stream while slab k computes; results come back per slab.  One slab = at most SLAB_RAYS rays / SLAB_PAIRS pairs.
 // indexed input (ssfm_ransac_batch_indexed): rays come from per-frame feature tables through per-pair match lists
-// dev != nullptr (ssfm_pairwise_from_features): the match lists are already on the device -- idx0 / idx1 / feat_rays are unused, the hooks stage, gather and collect
+// dev != nullptr (ssfm_pairwise_from_features, ssfm_pairwise5_from_features): the match lists are already on the device -- idx0 / idx1 / feat_rays are unused, the hooks stage, gather and collect
 struct RansacIndexed { int32_t num_frames; const int32_t* feat_ptr; const double* feat_rays; const int32_t* frame0; const int32_t* frame1; const int32_t* idx0; const int32_t* idx1;
                        ssfm::RansacDeviceLists* dev = nullptr; };
 // one workgroup per pair: u[i] = rays[off0 + idx0[i]], v[i] = rays[off1 + idx1[i]]
@@ -410,9 +410,9 @@ static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pa
                                    s.lists.p, s.E.p, s.S.p, s.R.p, s.mask.p, s.nin.p);
                 SSFM_HIP_CHECK(ctx, hipMemsetAsync(s.stats.p, 0, (size_t)2 * np * sizeof(unsigned), st));
             }
-            if (dev) { const int r = dev->lists(st, k % nslot, np, s.ptr.p, s.mask.p, s.nin.p, s.R.p); if (r) return r; }      // inside the kernel bracket
+            if (dev) { const int r = dev->lists(st, k % nslot, np, s.ptr.p, s.mask.p, s.nin.p, s.R.p, five ? s.E.p : nullptr, five ? s.T.p : nullptr); if (r) return r; }      // inside the kernel bracket
             SSFM_HIP_CHECK(ctx, hipEventRecord(kt1[k % nslot], st));
-            if (!dev) {                                       // (the hooks bring back the accepted pairs' R and inlier lists; E, the scores and the mask stay on the device)
+            if (!dev) {                                       // (the hooks bring back the accepted pairs' R -- five: t and E too -- and inlier lists; the scores and the mask stay on the device)
                 SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_res, s.E.p, (size_t)9 * np * sizeof(double), hipMemcpyDeviceToHost, st));
                 SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_res + 9 * (size_t)cap_pairs, s.R.p, (size_t)9 * np * sizeof(double), hipMemcpyDeviceToHost, st));
                 SSFM_HIP_CHECK(ctx, hipMemcpyAsync(s.h_res + 18 * (size_t)cap_pairs, s.S.p, (size_t)np * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -443,11 +443,16 @@ static int ransac_batch_impl(ssfm_ctx* ctx, int32_t num_pairs, const int32_t* pa
     return rc;
 }
 
+static ssfm_ransac_options ransac5_options(const ssfm_ransac_options* opt);
 namespace ssfm {
 int ransac_on_device_lists(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, int32_t num_pairs, const int32_t* pair_frame0, const int32_t* pair_frame1,
-                           const int32_t* pair_ptr, double sq_thresh, const ssfm_ransac_options& O, RansacDeviceLists* hooks, int32_t* num_inliers, uint32_t* stats) {
+                           const int32_t* pair_ptr, double sq_thresh, const ssfm_ransac_options& O, RansacDeviceLists* hooks, int32_t* num_inliers, uint32_t* stats,
+                           bool five, const char* who) {
     const RansacIndexed X{num_frames, feat_ptr, nullptr, pair_frame0, pair_frame1, nullptr, nullptr, hooks};
-    return ransac_batch_impl(ctx, num_pairs, pair_ptr, nullptr, nullptr, sq_thresh, O, nullptr, nullptr, nullptr, nullptr, num_inliers, nullptr, stats, &X);
+    if (!five) return ransac_batch_impl(ctx, num_pairs, pair_ptr, nullptr, nullptr, sq_thresh, O, nullptr, nullptr, nullptr, nullptr, num_inliers, nullptr, stats, &X);
+    const ssfm_ransac_options O5 = ransac5_options(&O);
+    return ransac_batch_impl(ctx, num_pairs, pair_ptr, nullptr, nullptr, sq_thresh, O5, nullptr, nullptr, nullptr, nullptr, num_inliers, nullptr, stats, &X, true, nullptr,
+                             who ? who : "ssfm_ransac5_batch_indexed");
 }
 }  // namespace ssfm
 

@@ -4,6 +4,8 @@
 // Writes <dir>/match_exhaustive.txt (one line per pair: index0 index1 n, then n x "j i") and <dir>/match_ratio.txt (match() of the first two keyframes with
 // ratio 1.5, same format) for the test to compare with its own matcher; prints DEMO_MATCH_RESULT.  Then estimate_pairwise_five_point on the same lists:
 // <dir>/five_point.txt (one line per accepted pair: index0 index1 n, n x "j i", the nine entries of R column-major as %.17g) and DEMO_FIVEPOINT_RESULT.
+// Then the same keyframes through estimate_pairwise_five_point_from_features: <dir>/five_point_front.txt in the same format and
+// DEMO_FIVEPOINT_FRONT_RESULT, whose equal compares with the two-call result.
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -14,6 +16,18 @@ static void write_line(FILE* f, int a, int b, const Matches& m) {
     std::fprintf(f, "%d %d %zu", a, b, m.size());
     for (auto& kv : m) std::fprintf(f, " %zu %zu", kv.first, kv.second);
     std::fprintf(f, "\n");
+}
+
+static void write_five(const std::string& path, const std::vector<ImageMatch>& ms) {
+    if (FILE* f = std::fopen(path.c_str(), "w")) {
+        for (const ImageMatch& m : ms) {
+            std::fprintf(f, "%d %d %zu", m.index0, m.index1, m.matches.size());
+            for (auto& kv : m.matches) std::fprintf(f, " %zu %zu", kv.first, kv.second);
+            for (int q = 0; q < 9; q++) std::fprintf(f, " %.17g", m.R[q]);
+            std::fprintf(f, "\n");
+        }
+        std::fclose(f);
+    }
 }
 
 int main(int argc, char** argv) {
@@ -41,15 +55,14 @@ int main(int argc, char** argv) {
                 match_same, a.size(), b.size(), loops_a, loops_b, equal);
     std::vector<ImageMatch> five;
     const int loops5 = estimate_pairwise_five_point(sfm.GetContext(), intrinsics, keyframes, all, thresh, min_inliers, five);
-    if (FILE* f = std::fopen((dir + "/five_point.txt").c_str(), "w")) {
-        for (const ImageMatch& m : five) {
-            std::fprintf(f, "%d %d %zu", m.index0, m.index1, m.matches.size());
-            for (auto& kv : m.matches) std::fprintf(f, " %zu %zu", kv.first, kv.second);
-            for (int q = 0; q < 9; q++) std::fprintf(f, " %.17g", m.R[q]);
-            std::fprintf(f, "\n");
-        }
-        std::fclose(f);
-    }
+    write_five(dir + "/five_point.txt", five);
     std::printf("DEMO_FIVEPOINT_RESULT accepted=%zu loops=%d\n", five.size(), loops5);
+    std::vector<ImageMatch> front;
+    const int loops5f = estimate_pairwise_five_point_from_features(sfm.GetContext(), intrinsics, keyframes, thresh, min_inliers, front);
+    write_five(dir + "/five_point_front.txt", front);
+    int equal5 = five.size() == front.size() && loops5 == loops5f;
+    for (size_t k = 0; equal5 && k < five.size(); k++)
+        equal5 = five[k].index0 == front[k].index0 && five[k].index1 == front[k].index1 && five[k].matches == front[k].matches && five[k].R == front[k].R;
+    std::printf("DEMO_FIVEPOINT_FRONT_RESULT accepted=%zu loops=%d equal=%d\n", front.size(), loops5f, equal5);
     return 0;
 }

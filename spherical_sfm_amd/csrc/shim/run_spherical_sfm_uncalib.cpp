@@ -8,7 +8,8 @@
 // -viewgraph: the frames need not be in capture order -- the focal search chains its trial rotations along a breadth-first spanning tree of the matches
 // (find_best_focal_length_random with sequential = false -> ssfm_focal_search_graph) instead of along the matches (k-1, k).  Without it nothing changes.
 // -fivepoint: the pairwise stage is general relative pose (estimate_pairwise_five_point, examples/run_spherical_sfm_uncalib.cpp:107-110) instead of the spherical
-// three-point estimator: with -match on the lists of match_exhaustive, without it on the matches of matches.dat, whose rotations it replaces.
+// three-point estimator: with -match in one device call from the feature tables (estimate_pairwise_five_point_from_features: the match lists stay on the
+// device), without it on the matches of matches.dat, whose rotations it replaces.
 //   run_spherical_sfm_uncalib -output <dir with keyframes.txt, features.dat, matches.dat> -width W -height H [-generalba] [-inward]
 //                             [-match] [-fivepoint] [-inlierthresh T] [-mininliers N] [-viewgraph]
 #include <cstdio>
@@ -46,10 +47,11 @@ int main(int argc, char** argv) {
     SfM sfm_probe(Intrinsics(focal_guess, centerx, centery));                                       // owns the library context for the pairwise stage and the search
     int loop_closures = -1;
     if (fivepoint) {                                                                                // :107-110
-        std::vector<ImageMatch> all;
-        if (match_mode) match_exhaustive(sfm_probe.GetContext(), keyframes, all); else all.swap(image_matches);
-        image_matches.clear();
-        loop_closures = estimate_pairwise_five_point(sfm_probe.GetContext(), Intrinsics(focal_guess, centerx, centery), keyframes, all, inlierthresh, mininliers, image_matches);
+        if (match_mode) loop_closures = estimate_pairwise_five_point_from_features(sfm_probe.GetContext(), Intrinsics(focal_guess, centerx, centery), keyframes, inlierthresh, mininliers, image_matches);
+        else {
+            std::vector<ImageMatch> all; all.swap(image_matches);
+            loop_closures = estimate_pairwise_five_point(sfm_probe.GetContext(), Intrinsics(focal_guess, centerx, centery), keyframes, all, inlierthresh, mininliers, image_matches);
+        }
         if (loop_closures == 0) { std::cout << "error: no loop closures found\n"; return 1; }
         find_largest_connected_component(keyframes, image_matches);
         if (image_matches.empty()) { std::cout << "error: no matches found\n"; return 1; }

@@ -171,26 +171,32 @@ void match_exhaustive(ssfm_ctx* ctx, const std::vector<Keyframe>& keyframes, std
     }
 }
 
-int estimate_pairwise_from_features(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, double inlier_threshold, int min_num_inliers,
-                                    bool inward, std::vector<ImageMatch>& image_matches_out) {
+// the two one-call front ends: exhaustive pairs, capacity bounds that cannot miss, the loop-closure count (five: ssfm_pairwise5_from_features, no `inward`)
+static int pairwise_front(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, double inlier_threshold, int min_num_inliers,
+                          bool five, bool inward, std::vector<ImageMatch>& image_matches_out) {
     if (keyframes.size() < 2) return 0;
     const double kinv = 1.0 / intrinsics.focal;
-    const double sq_thresh = inlier_threshold * inlier_threshold * kinv * kinv;           // :315
+    const double sq_thresh = inlier_threshold * inlier_threshold * kinv * kinv;           // :315, :440
     std::vector<const Features*> fs; for (const Keyframe& k : keyframes) fs.push_back(&k.features);
     std::vector<int32_t> feat_ptr, pf0, pf1; std::vector<float> descs; std::vector<double> rays;
     feature_tables(fs, &intrinsics, feat_ptr, descs, &rays);
     exhaustive_pairs(keyframes, pf0, pf1);
     ssfm_ransac_options O; ssfm_ransac_default_options(&O);
-    O.min_num_inliers = min_num_inliers; O.inward = inward ? 1 : 0; O.final_least_squares = 1;                                 // :316-318
+    O.min_num_inliers = min_num_inliers;
+    if (!five) { O.inward = inward ? 1 : 0; O.final_least_squares = 1; }                  // :316-318 (five: :441-445, the LO options it sets have no effect on that estimator)
     const int P = (int)pf0.size();
     int64_t pair_cap = P, inl_cap = 0, needed[2] = {0, 0};
     for (int p = 0; p < P; p++) inl_cap += std::min(feat_ptr[pf0[p] + 1] - feat_ptr[pf0[p]], feat_ptr[pf1[p] + 1] - feat_ptr[pf1[p]]);   // a pair has at most min(n0, n1) matches: never a miss
-    std::vector<int32_t> acc, nin, ptr, i0, i1; std::vector<double> R;
+    std::vector<int32_t> acc, nin, ptr, i0, i1; std::vector<double> R, t;
     for (int attempt = 0; attempt < 2; attempt++) {                                       // the capacity protocol (the bounds above cannot miss; a retry would repeat all the work)
         acc.assign((size_t)std::max<int64_t>(pair_cap, 1), 0); nin.assign(acc.size(), 0); ptr.assign((size_t)pair_cap + 1, 0); R.assign(9 * acc.size(), 0.0);
         i0.assign((size_t)std::max<int64_t>(inl_cap, 1), 0); i1.assign(i0.size(), 0);
-        const int rc = ssfm_pairwise_from_features(ctx, (int32_t)fs.size(), feat_ptr.data(), descs.data(), rays.data(), P, pf0.data(), pf1.data(), nullptr, &O, sq_thresh,
-                                                   pair_cap, inl_cap, needed, acc.data(), R.data(), nin.data(), ptr.data(), i0.data(), i1.data(), nullptr, nullptr, nullptr);
+        if (five) t.assign(3 * acc.size(), 0.0);                                          // (ImageMatch has no place for t; E is not asked for)
+        const int rc = five ? ssfm_pairwise5_from_features(ctx, (int32_t)fs.size(), feat_ptr.data(), descs.data(), rays.data(), P, pf0.data(), pf1.data(), nullptr, &O, sq_thresh,
+                                                           pair_cap, inl_cap, needed, acc.data(), R.data(), t.data(), nullptr, nin.data(), ptr.data(), i0.data(), i1.data(),
+                                                           nullptr, nullptr, nullptr)
+                            : ssfm_pairwise_from_features(ctx, (int32_t)fs.size(), feat_ptr.data(), descs.data(), rays.data(), P, pf0.data(), pf1.data(), nullptr, &O, sq_thresh,
+                                                          pair_cap, inl_cap, needed, acc.data(), R.data(), nin.data(), ptr.data(), i0.data(), i1.data(), nullptr, nullptr, nullptr);
         if (rc == SSFM_OK) break;
         if (attempt == 0 && (needed[0] > pair_cap || needed[1] > inl_cap)) { pair_cap = needed[0]; inl_cap = needed[1]; continue; }
         std::cout << "error: " << ssfm_last_error(ctx) << "\n"; std::exit(1);
@@ -204,6 +210,16 @@ int estimate_pairwise_from_features(ssfm_ctx* ctx, const Intrinsics& intrinsics,
         image_matches_out.push_back(ImageMatch(index0, index1, inl, Rk));
     }
     return loop_closure_count;
+}
+
+int estimate_pairwise_from_features(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, double inlier_threshold, int min_num_inliers,
+                                    bool inward, std::vector<ImageMatch>& image_matches_out) {
+    return pairwise_front(ctx, intrinsics, keyframes, inlier_threshold, min_num_inliers, false, inward, image_matches_out);
+}
+
+int estimate_pairwise_five_point_from_features(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, double inlier_threshold,
+                                               int min_num_inliers, std::vector<ImageMatch>& image_matches_out) {
+    return pairwise_front(ctx, intrinsics, keyframes, inlier_threshold, min_num_inliers, true, false, image_matches_out);
 }
 
 void initialize_rotations_sequential(int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations) {

@@ -79,6 +79,12 @@ bool read_features(const std::string& outputpath, std::vector<Keyframe>& keyfram
 int estimate_pairwise_from_features(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, double inlier_threshold, int min_num_inliers,
                                     bool inward, std::vector<ImageMatch>& image_matches_out);
 
+// match_exhaustive + estimate_pairwise_five_point in one device call (ssfm_pairwise5_from_features), built like estimate_pairwise_from_features: all pairs
+// index0 < index1, capacity bounds that cannot miss, the loop-closure count.  Same result and return value as match_exhaustive followed by
+// estimate_pairwise_five_point.  Single-GPU: the context must not carry a communicator.
+int estimate_pairwise_five_point_from_features(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, double inlier_threshold,
+                                               int min_num_inliers, std::vector<ImageMatch>& image_matches_out);
+
 void initialize_rotations_sequential(int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations);   // tools.cpp:794-813
 double refine_rotations(ssfm_ctx* ctx, int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations); // tools.cpp:851-860
 // tools.cpp:862-955: tracks (ssfm_build_tracks, ids bit-exact with the reference's AddPoint sequence), cameras, observations, Retriangulate
