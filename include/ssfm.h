@@ -580,6 +580,45 @@ int ssfm_rot_l1_init(ssfm_ctx* ctx, int32_t num_cameras, int32_t num_edges, cons
                      const double* rel_rotations, int32_t root, const ssfm_rot_l1_options* opt /* NULL = defaults */,
                      double* rotations_out /* 9 n, column-major */, double* residual_out /* E, may be NULL */, ssfm_rot_l1_summary* s);
 
+/* ---- keypoint selection: adaptive non-maximal suppression, batched over frames ---------------------------------------------------------
+ * ssfm_anms_batch: adaptiveNonMaximalSuppresion (examples/spherical_sfm_tools.cpp:76-123), the thinning step of DetectorTracker::detect (:179-208),
+ *   for every frame in one device call.  Frame f owns the keypoints kp_ptr[f] .. kp_ptr[f + 1] of xy ([2 * total]: x, y) and response ([total]).
+ *   Per frame, with n keypoints and k = num_to_keep[f]:
+ *     n < k: the keypoints are returned unchanged -- keep_idx is 0 .. n-1, the radii are DBL_MAX.
+ *     Otherwise, in the total order (response descending, original index ascending), precedes(j, i) = response_j > response_i ||
+ *     (response_j == response_i && j < i):
+ *       thr_i    = response_i * 1.11f (a float product),
+ *       radius_i = sqrt(min over {j : response_j > thr_i && precedes(j, i)} of (double)dx * dx + (double)dy * dy), dx and dy float differences;
+ *                  DBL_MAX when no j qualifies (a difference that overflows to infinity, or is NaN, never lowers a radius: std::min in the reference),
+ *       decision = element k (0-based) of the radii sorted descending,
+ *       kept: every i with radius_i >= decision, in the total order.  At least k + 1 keypoints survive, more when radii tie.
+ *     This is the reference's loop (sort by response; for each i the prefix of j with response_j > thr_i) for every tie order std::sort may pick when the
+ *     responses are non-negative, and for the stable order when some are negative.
+ *   keep_ptr [num_frames + 1], keep_idx: frame-local original indices, frame f's at keep_ptr[f] .. keep_ptr[f + 1]; a frame never keeps more than it has, so
+ *   capacity `total` always suffices and there is no counting call.  radius: [total], per INPUT keypoint, may be NULL.
+ *   Three deviations from the reference:
+ *     n == k: the reference reads one element past its radii array; here every keypoint is returned, in the total order;
+ *     a NaN response (undefined behaviour in std::sort) is refused;
+ *     among equal responses the output order is by original index (std::sort leaves it unspecified).
+ *   SSFM_ERR_INVALID before anything is launched, the message prefixed with the function's name: kp_ptr not starting at 0 or not ascending, a negative
+ *   num_to_keep, a NaN response, force_j_chunks < 0 (arguments, options, kp_ptr, num_to_keep, responses, then the context).  num_frames = 0 and empty frames
+ *   are valid.  Single-GPU: a context with a communicator is refused.
+ *   force_j_chunks: 0 lets the planner decide how many chunks a frame's j range is cut into (frames that cannot fill the device alone are cut); k > 0 cuts
+ *   every frame into k chunks.  The chunks combine by integer atomics only: the result is the same bits for every cut and every run.
+ * ssfm_anms_batch_host: the same contract on the host (sort, prefix loop with the early exit, selection), num_threads threads over frames and blocks of a
+ *   frame.  No context; the native check and the CPU side of scripts/anms_timing.py.  Never called by ssfm_anms_batch.
+ * ssfm_anms_last_kernel_ms: device time between the first and the last launch of the context's last ssfm_anms_batch call (one hipEvent pair). */
+typedef struct {
+    int32_t force_j_chunks;   /* 0 = planner decides */
+    int32_t reserved;
+} ssfm_anms_options;
+void ssfm_anms_default_options(ssfm_anms_options* o);
+int ssfm_anms_batch(ssfm_ctx* ctx, int32_t num_frames, const int32_t* kp_ptr, const float* xy, const float* response, const int32_t* num_to_keep,
+                    const ssfm_anms_options* opt /* NULL = defaults */, int32_t* keep_ptr, int32_t* keep_idx, double* radius /* may be NULL */);
+int ssfm_anms_batch_host(int32_t num_frames, const int32_t* kp_ptr, const float* xy, const float* response, const int32_t* num_to_keep, int32_t num_threads,
+                         int32_t* keep_ptr, int32_t* keep_idx, double* radius /* may be NULL */);
+int ssfm_anms_last_kernel_ms(ssfm_ctx* ctx, double* ms);
+
 /* ---- SfM::Retriangulate (src/sfm.cpp:156-192) ------------------------------------------------------------------
  * Re-estimates EVERY point of the problem from its observations and the current cameras/focal with the per-point
  * ransac_lib::LocallyOptimizedMSAC<Point, ..., TriangulationEstimator> of the reference (src/triangulation_estimator.cpp:46-127,

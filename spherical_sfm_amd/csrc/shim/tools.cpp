@@ -158,6 +158,58 @@ void match(ssfm_ctx* ctx, const Features& features0, const Features& features1, 
     for (int32_t k = mp[0]; k < mp[1]; k++) m01[(size_t)m0[k]] = (size_t)m1[k];
 }
 
+void adaptiveNonMaximalSuppresion(ssfm_ctx* ctx, std::vector<std::vector<KeyPoint>>& keypoints_per_frame, const std::vector<int>& numToKeep) {
+    const int F = (int)keypoints_per_frame.size();
+    if ((int)numToKeep.size() != F) { std::cout << "error: adaptiveNonMaximalSuppresion: one numToKeep per frame\n"; std::exit(1); }
+    std::vector<int32_t> kp_ptr((size_t)F + 1, 0), keep(numToKeep.begin(), numToKeep.end()), keep_ptr((size_t)F + 1, 0);
+    for (int f = 0; f < F; f++) kp_ptr[(size_t)f + 1] = kp_ptr[(size_t)f] + (int32_t)keypoints_per_frame[(size_t)f].size();
+    const size_t total = (size_t)kp_ptr[(size_t)F];
+    std::vector<float> xy(2 * std::max<size_t>(total, 1)), response(std::max<size_t>(total, 1));
+    std::vector<int32_t> keep_idx(std::max<size_t>(total, 1));
+    for (int f = 0; f < F; f++)
+        for (size_t k = 0; k < keypoints_per_frame[(size_t)f].size(); k++) {
+            const KeyPoint& kp = keypoints_per_frame[(size_t)f][k]; const size_t g = (size_t)kp_ptr[(size_t)f] + k;
+            xy[2 * g] = kp.pt.x; xy[2 * g + 1] = kp.pt.y; response[g] = kp.response;
+        }
+    if (ssfm_anms_batch(ctx, F, kp_ptr.data(), xy.data(), response.data(), keep.data(), nullptr, keep_ptr.data(), keep_idx.data(), nullptr) != SSFM_OK) {
+        std::cout << "error: " << ssfm_last_error(ctx) << "\n"; std::exit(1);
+    }
+    for (int f = 0; f < F; f++) {
+        std::vector<KeyPoint>& kps = keypoints_per_frame[(size_t)f];
+        if ((int)kps.size() < numToKeep[(size_t)f]) continue;                               // :79, left as they are
+        std::vector<KeyPoint> anmsPts;
+        for (int32_t q = keep_ptr[(size_t)f]; q < keep_ptr[(size_t)f + 1]; q++) anmsPts.push_back(kps[(size_t)keep_idx[(size_t)q]]);
+        anmsPts.swap(kps);
+    }
+}
+
+void adaptiveNonMaximalSuppresion(ssfm_ctx* ctx, std::vector<KeyPoint>& keypoints, const int numToKeep) {
+    std::vector<std::vector<KeyPoint>> one(1); one[0].swap(keypoints);
+    adaptiveNonMaximalSuppresion(ctx, one, std::vector<int>(1, numToKeep));
+    keypoints.swap(one[0]);
+}
+
+void select_keypoints(ssfm_ctx* ctx, std::vector<Features*>& features, std::vector<std::vector<KeyPoint>>& keypoints_per_frame) {
+    if (features.size() != keypoints_per_frame.size()) { std::cout << "error: select_keypoints: one Features per frame\n"; std::exit(1); }
+    std::vector<std::vector<KeyPoint>> live; std::vector<int> ntokeep; std::vector<size_t> frame;
+    for (size_t f = 0; f < features.size(); f++) {
+        const int n = std::max(0, 4000 - (int)features[f]->points.size());                  // :186
+        if (n == 0) { keypoints_per_frame[f].clear(); continue; }                           // :187
+        live.emplace_back(); live.back().swap(keypoints_per_frame[f]); ntokeep.push_back(n); frame.push_back(f);
+    }
+    adaptiveNonMaximalSuppresion(ctx, live, ntokeep);
+    for (size_t k = 0; k < live.size(); k++) {
+        for (const KeyPoint& kp : live[k]) features[frame[k]]->points.push_back(kp.pt);     // :204
+        keypoints_per_frame[frame[k]].swap(live[k]);
+    }
+}
+
+void select_keypoints(ssfm_ctx* ctx, Features& features, std::vector<KeyPoint>& keypoints) {
+    std::vector<Features*> fs(1, &features); std::vector<std::vector<KeyPoint>> one(1); one[0].swap(keypoints);
+    select_keypoints(ctx, fs, one);
+    keypoints.swap(one[0]);
+}
+
 void match_exhaustive(ssfm_ctx* ctx, const std::vector<Keyframe>& keyframes, std::vector<ImageMatch>& image_matches) {
     if (keyframes.size() < 2) return;
     std::vector<const Features*> fs; for (const Keyframe& k : keyframes) fs.push_back(&k.features);

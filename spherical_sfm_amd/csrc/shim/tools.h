@@ -36,6 +36,24 @@ struct Keyframe {                                         // spherical_sfm_tools
     Keyframe(int _index, const std::string& _name, const Features& _features) : index(_index), name(_name), features(_features) {}
 };
 
+struct KeyPoint {                                         // cv::KeyPoint's data members, as a POD
+    Point2f pt; float size, angle, response; int octave, class_id;
+};
+
+// adaptiveNonMaximalSuppresion (spherical_sfm_tools.cpp:76-123) over ssfm_anms_batch, the reference's signature plus the context argument: fewer keypoints than
+// numToKeep are left as they are; otherwise the survivors replace `keypoints`, strongest response first.  Where the reference is open or undefined (include/ssfm.h):
+// equal responses come out by their position in the input, keypoints.size() == numToKeep returns all of them sorted, a NaN response is an error.
+// The batched overload thins every frame in ONE device call (the reference runs one frame per OpenMP thread, :299-306).  Exits on an error of the library.
+void adaptiveNonMaximalSuppresion(ssfm_ctx* ctx, std::vector<KeyPoint>& keypoints, const int numToKeep);
+void adaptiveNonMaximalSuppresion(ssfm_ctx* ctx, std::vector<std::vector<KeyPoint>>& keypoints_per_frame, const std::vector<int>& numToKeep);
+
+// The selection of DetectorTracker::detect (:186-198) without the detector: ntokeep = max(0, 4000 - features.points.size()); 0 selects nothing (keypoints is
+// emptied, features stays); otherwise keypoints is thinned to ntokeep and the survivors' positions are appended to features.points, as :202-207 does.  The
+// descriptors and colours of the appended points need the image (sift->compute, sample_image) and are the caller's to append.  The batched form makes one
+// device call for all frames.
+void select_keypoints(ssfm_ctx* ctx, Features& features, std::vector<KeyPoint>& keypoints);
+void select_keypoints(ssfm_ctx* ctx, std::vector<Features*>& features, std::vector<std::vector<KeyPoint>>& keypoints_per_frame);
+
 // keyframes.txt / features.dat / matches.dat (examples/spherical_sfm_io.cpp:10-120).  The reference prints the keyframe name with
 // "%s" of a std::string object and reads back only the indices; here the name is written as text and skipped on input.
 void write_feature_tracks(const std::string& outputpath, const std::vector<Keyframe>& keyframes, const std::vector<ImageMatch>& image_matches);

@@ -29,6 +29,7 @@ struct ssfm_ctx {
     double ransac_kernel_ms = 0.0;      // device time of the kernels of the last ssfm_ransac_batch* call (hipEvent brackets per slab), ssfm_ransac_last_kernel_ms
     double match_kernel_ms = 0.0;       // the same for the last ssfm_match_pairs call, ssfm_match_last_kernel_ms
     double front_kernel_ms = 0.0;       // the same for the last ssfm_pairwise_from_features / ssfm_pairwise5_from_features call (its matching + its RANSAC slabs, hand-over kernels included)
+    double anms_kernel_ms = 0.0;        // the same for the last ssfm_anms_batch call (one event pair round its launches), ssfm_anms_last_kernel_ms
 };
 
 namespace ssfm {
