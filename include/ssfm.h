@@ -580,6 +580,38 @@ int ssfm_rot_l1_init(ssfm_ctx* ctx, int32_t num_cameras, int32_t num_edges, cons
                      const double* rel_rotations, int32_t root, const ssfm_rot_l1_options* opt /* NULL = defaults */,
                      double* rotations_out /* 9 n, column-major */, double* residual_out /* E, may be NULL */, ssfm_rot_l1_summary* s);
 
+/* ---- robust focal search for a view graph: one L1 solve per trial focal on the device --------------------------------------------------
+ * ssfm_focal_search_l1: ssfm_focal_search_graph whose trials do not inherit the wrong edges of the spanning tree.  Defined per trial t by
+ *   composition of the two calls above:
+ *     1. rel_t: the matches re-derived at focals[t] -- the transform_image_matches step of ssfm_focal_search_graph, the same device functions
+ *        in the same order (its rel_rotations_best for the single trial focals[t]);
+ *     2. (R_t, residual_t, iterations_t): the algorithm of ssfm_rot_l1_init on (index0, index1, rel_t, root, opt) as stated above -- used
+ *        edges and free nodes by the walk of ssfm_view_graph_tree(root), the tree chain as the start, w_e = 1 / max(|v_e|, weight_floor),
+ *        the three columns in lockstep through Jacobi-preconditioned CG with the stopping test before each iteration and the cap, the update
+ *        R_i <- R_i so3exp(x_i), the end after the update when step < step_tolerance or at max_iterations;
+ *     3. costs[t] = sum |v_e| over the used edges at R_t (final_cost); get_costs[t] = the cost ssfm_focal_search_graph takes, at R_t and
+ *        rel_t; iterations[t] = the outer iterations run.
+ *   *best_trial: the first minimum of costs (strict <).  rotations_best (9 n) and rel_rotations_best (9 E), column-major, are those of the
+ *   best trial; residual_best[e] = |v_e| there, -1 for an unused edge.  Every output may be NULL.
+ *   The tree and the adjacency are built once per call; the whole iteration of a trial runs inside one launch, a workgroup per trial.  The
+ *   sums of a trial are taken in an order fixed by (n, num_edges, adjacency): its outputs do not depend on its position among the trials, on
+ *   num_trials, on the slab of trials it is run in (SSFM_FOCAL_L1_SLAB_TRIALS overrides the slab size) or on where the solver's vectors
+ *   are kept (LDS when they fit, SSFM_FOCAL_L1_FORCE_GLOBAL=1 forces global memory); two calls return the same bits.
+ *   The sums are not taken in the order of ssfm_rot_l1_init (a lane per node here, a wave per node there): the two agree to rounding.
+ *   SSFM_ERR_INVALID before anything is launched, the message prefixed "ssfm_focal_search_l1": what ssfm_focal_search_graph refuses
+ *   (n, num_edges, num_trials <= 0, a NULL input), the options ssfm_rot_l1_init refuses, an index or the root out of range (in this order),
+ *   then a NULL context or one with a communicator.
+ *   ssfm_focal_l1_default_options: ssfm_rot_l1_default_options with max_iterations = 10 ("Robust focal search").
+ *   costs is not normalised by the size of the relative rotations, which grow with the trial focal: where a large part of the edges is wrong,
+ *   the lower end of a wide trial range can undercut the true focal ("Robust focal search", Open).
+ *   kernel_ms: device time of the launches, summed over the slabs. */
+void ssfm_focal_l1_default_options(ssfm_rot_l1_options* o);
+int ssfm_focal_search_l1(ssfm_ctx* ctx, int32_t n, int32_t num_edges, const int32_t* index0, const int32_t* index1,
+                         const double* rel_rotations, int32_t inward, double focal_guess, int32_t num_trials, const double* focals,
+                         int32_t root, const ssfm_rot_l1_options* opt /* NULL = ssfm_focal_l1_default_options */,
+                         double* costs, double* get_costs, int32_t* iterations, int32_t* best_trial,
+                         double* rotations_best, double* rel_rotations_best, double* residual_best, double* kernel_ms);
+
 /* ---- keypoint selection: adaptive non-maximal suppression, batched over frames ---------------------------------------------------------
  * ssfm_anms_batch: adaptiveNonMaximalSuppresion (examples/spherical_sfm_tools.cpp:76-123), the thinning step of DetectorTracker::detect (:179-208),
  *   for every frame in one device call.  Frame f owns the keypoints kp_ptr[f] .. kp_ptr[f + 1] of xy ([2 * total]: x, y) and response ([total]).

@@ -113,6 +113,7 @@ DECLARED_SYMBOLS = [
     "ssfm_pairwise_from_features", "ssfm_pairwise5_from_features", "ssfm_pairwise_front_last_kernel_ms",
     "ssfm_triplet_filter", "ssfm_view_graph_tree", "ssfm_focal_search_graph",
     "ssfm_rot_l1_default_options", "ssfm_rot_l1_init",
+    "ssfm_focal_l1_default_options", "ssfm_focal_search_l1",
     "ssfm_anms_default_options", "ssfm_anms_batch", "ssfm_anms_batch_host", "ssfm_anms_last_kernel_ms",
 ]
 
@@ -242,6 +243,10 @@ def lib():
     L.ssfm_rot_l1_init.argtypes = [vp, C.c_int32, C.c_int32, c_i32_p, c_i32_p, c_double_p, C.c_int32, C.POINTER(RotL1OptionsC), c_double_p, c_double_p,
                                    C.POINTER(RotL1SummaryC)]
     L.ssfm_rot_l1_init.restype = C.c_int
+    L.ssfm_focal_l1_default_options.argtypes = [C.POINTER(RotL1OptionsC)]; L.ssfm_focal_l1_default_options.restype = None
+    L.ssfm_focal_search_l1.argtypes = [vp, C.c_int32, C.c_int32, c_i32_p, c_i32_p, c_double_p, C.c_int32, C.c_double, C.c_int32, c_double_p, C.c_int32,
+                                       C.POINTER(RotL1OptionsC), c_double_p, c_double_p, c_i32_p, c_i32_p, c_double_p, c_double_p, c_double_p, c_double_p]
+    L.ssfm_focal_search_l1.restype = C.c_int
     L.ssfm_anms_default_options.argtypes = [C.POINTER(AnmsOptionsC)]; L.ssfm_anms_default_options.restype = None
     L.ssfm_anms_batch.argtypes = [vp, C.c_int32, c_i32_p, c_float_p, c_float_p, c_i32_p, C.POINTER(AnmsOptionsC), c_i32_p, c_i32_p, c_double_p]; L.ssfm_anms_batch.restype = C.c_int
     L.ssfm_anms_batch_host.argtypes = [C.c_int32, c_i32_p, c_float_p, c_float_p, c_i32_p, C.c_int32, c_i32_p, c_i32_p, c_double_p]; L.ssfm_anms_batch_host.restype = C.c_int

@@ -7,11 +7,16 @@
 // find_largest_connected_component (:96-122).
 // -viewgraph: the frames need not be in capture order -- the focal search chains its trial rotations along a breadth-first spanning tree of the matches
 // (find_best_focal_length_random with sequential = false -> ssfm_focal_search_graph) instead of along the matches (k-1, k).  Without it nothing changes.
+// -rotinit l1 (with -viewgraph; default: tree) [-rotinitthresh DEG, default 2]: the focal search solves the rotations of every trial robustly and judges the trial
+// by the sum of the residuals (find_best_focal_length_random_l1 -> ssfm_focal_search_l1): a wrong match on a tree edge no longer spoils the cost of every trial.
+// At the found focal the matches whose converged L1 residual exceeds the threshold are dropped, find_largest_connected_component runs once more, and the joint
+// refinement starts from the L1 rotations of what is left; rotinit.txt lists every pair with its residual, ROTINIT_RESULT the counts.
 // -fivepoint: the pairwise stage is general relative pose (estimate_pairwise_five_point, examples/run_spherical_sfm_uncalib.cpp:107-110) instead of the spherical
 // three-point estimator: with -match in one device call from the feature tables (estimate_pairwise_five_point_from_features: the match lists stay on the
 // device), without it on the matches of matches.dat, whose rotations it replaces.
 //   run_spherical_sfm_uncalib -output <dir with keyframes.txt, features.dat, matches.dat> -width W -height H [-generalba] [-inward]
-//                             [-match] [-fivepoint] [-inlierthresh T] [-mininliers N] [-viewgraph]
+//                             [-match] [-fivepoint] [-inlierthresh T] [-mininliers N] [-viewgraph [-rotinit tree|l1] [-rotinitthresh DEG]]
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -20,6 +25,7 @@ using namespace sphericalsfm;
 
 int main(int argc, char** argv) {
     std::string output; bool inward = false, generalba = false, match_mode = false, viewgraph = false, fivepoint = false; int width = 0, height = 0, num_trials = 1024, mininliers = 100; unsigned seed = 0; double inlierthresh = 2.0;
+    bool rotinit_l1 = false; double rotinit_thresh_deg = 2.0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "-output" && i + 1 < argc) output = argv[++i];
@@ -35,9 +41,16 @@ int main(int argc, char** argv) {
         else if (a == "-mininliers" && i + 1 < argc) mininliers = std::atoi(argv[++i]);
         else if (a == "-sequential") viewgraph = false;
         else if (a == "-viewgraph") viewgraph = true;
+        else if (a == "-rotinit" && i + 1 < argc) {
+            const std::string o = argv[++i];
+            if (o == "l1") rotinit_l1 = true; else if (o == "tree") rotinit_l1 = false;
+            else { std::cout << "unknown rotation initialisation " << o << " (tree or l1)\n"; return 2; }
+        }
+        else if (a == "-rotinitthresh" && i + 1 < argc) rotinit_thresh_deg = std::atof(argv[++i]);
         else { std::cout << "unknown argument " << a << "\n"; return 2; }
     }
     if (output.empty() || width <= 0 || height <= 0) { std::cout << "usage: run_spherical_sfm_uncalib -output <dir> -width W -height H [-generalba] [-inward]\n"; return 2; }
+    if (rotinit_l1 && !viewgraph) { std::cout << "-rotinit l1 needs -viewgraph\n"; return 2; }
     std::vector<Keyframe> keyframes; std::vector<ImageMatch> image_matches;
     const double focal_guess = (width + height) / 2, centerx = width / 2, centery = height / 2;     // :101-103 (integer division as in the reference)
     if (match_mode ? !read_features(output, keyframes) : (!read_feature_tracks(output, keyframes, image_matches) || image_matches.empty())) { std::cout << "error: no matches found\n"; return 1; }
@@ -62,7 +75,22 @@ int main(int argc, char** argv) {
         if (image_matches.empty()) { std::cout << "error: no matches found\n"; return 1; }
     }
     std::vector<Mat3> rotations; double focal_new = focal_guess;
-    if (!find_best_focal_length_random(sfm_probe.GetContext(), (int)keyframes.size(), image_matches, inward, !viewgraph, focal_guess, min_focal, max_focal,
+    if (rotinit_l1) {
+        FocalL1Summary l1;
+        const bool ok = find_best_focal_length_random_l1(sfm_probe.GetContext(), keyframes, image_matches, inward, focal_guess, min_focal, max_focal, num_trials, rotations,
+                                                         focal_new, seed, (output + "/costs.txt").c_str(), rotinit_thresh_deg * M_PI / 180.0, &l1);
+        if (FILE* f = std::fopen((output + "/rotinit.txt").c_str(), "w")) {                          // frame numbers of the pair, residual in degrees, 1 = kept
+            for (size_t e = 0; e < l1.residual.size(); e++)
+                std::fprintf(f, "%d %d %f %d\n", l1.frame0[e], l1.frame1[e], l1.residual[e] * 180.0 / M_PI,
+                             l1.residual[e] >= 0.0 && l1.residual[e] <= rotinit_thresh_deg * M_PI / 180.0 ? 1 : 0);
+            std::fclose(f);
+        }
+        if (!ok) { std::cout << "ERROR: could not find any acceptable focal length\n"; return 1; }
+        std::printf("ROTINIT_RESULT edges_in=%zu edges_kept=%zu cameras_in=%zu cameras_kept=%zu iterations=%d cg_iterations=%lld cost_initial=%.6e cost_final=%.6e "
+                    "focal_search_l1=%.6f search_kernel_ms=%.3f\n", l1.edges_in, l1.edges_kept, l1.cameras_in, l1.cameras_kept, l1.l1.iterations,
+                    (long long)l1.l1.pcg_iterations_total, l1.l1.initial_cost, l1.l1.final_cost, l1.focal_search, l1.search_kernel_ms);
+    }
+    else if (!find_best_focal_length_random(sfm_probe.GetContext(), (int)keyframes.size(), image_matches, inward, !viewgraph, focal_guess, min_focal, max_focal,
                                        num_trials, rotations, focal_new, seed, (output + "/costs.txt").c_str())) {
         std::cout << "ERROR: could not find any acceptable focal length\n"; return 1;
     }

@@ -425,4 +425,51 @@ bool find_best_focal_length_random(ssfm_ctx* ctx, int num_cameras, std::vector<I
     return true;
 }
 
+bool find_best_focal_length_random_l1(ssfm_ctx* ctx, std::vector<Keyframe>& keyframes, std::vector<ImageMatch>& image_matches, bool inward, double focal_guess,
+                                      double min_focal, double max_focal, int num_trials, std::vector<Mat3>& rotations, double& best_focal, unsigned seed,
+                                      const char* costs_path, double thresh_rad, FocalL1Summary* summary) {
+    const int num_cameras = (int)keyframes.size(), E = (int)image_matches.size();
+    std::vector<int32_t> i0(E), i1(E); std::vector<double> rel((size_t)9 * E);
+    for (int e = 0; e < E; e++) { i0[e] = image_matches[e].index0; i1[e] = image_matches[e].index1; for (int k = 0; k < 9; k++) rel[9 * (size_t)e + k] = image_matches[e].R[k]; }
+    std::mt19937 gen(seed);
+    std::uniform_real_distribution<double> dist(min_focal, max_focal);                    // as find_best_focal_length_random draws
+    std::vector<double> focals(std::max(num_trials, 0)), costs(focals.size()), get_costs(focals.size());
+    for (int t = 0; t < num_trials; t++) focals[t] = dist(gen);
+    int32_t best = 0; double kernel_ms = 0.0;
+    std::vector<double> rel_best((size_t)9 * E);
+    if (ssfm_focal_search_l1(ctx, num_cameras, E, i0.data(), i1.data(), rel.data(), inward ? 1 : 0, focal_guess, num_trials, focals.data(), 0, nullptr, costs.data(),
+                             get_costs.data(), nullptr, &best, nullptr, rel_best.data(), nullptr, &kernel_ms) != SSFM_OK) {
+        std::cout << "error: " << ssfm_last_error(ctx) << "\n"; return false;
+    }
+    if (costs_path) {
+        if (FILE* f = std::fopen(costs_path, "w")) { for (int t = 0; t < num_trials; t++) std::fprintf(f, "%d %lf %lf %lf\n", t, focals[t], costs[t], get_costs[t]); std::fclose(f); }
+    }
+    best_focal = focals[best];
+    std::cout << "before optimization: " << best_focal << "\n";
+    FocalL1Summary S;
+    S.edges_in = (size_t)E; S.cameras_in = keyframes.size(); S.best_trial = best; S.focal_search = best_focal; S.search_cost = costs[best]; S.search_kernel_ms = kernel_ms;
+    // the matches at the found focal; converged residuals there, the cut, the component
+    for (int e = 0; e < E; e++) for (int k = 0; k < 9; k++) image_matches[e].R[k] = rel_best[9 * (size_t)e + k];
+    std::vector<double> residuals;
+    initialize_rotations_l1(ctx, num_cameras, image_matches, rotations, residuals, 0, &S.l1);
+    S.frame0.resize(E); S.frame1.resize(E); S.residual = residuals;
+    for (int e = 0; e < E; e++) { S.frame0[e] = keyframes[image_matches[e].index0].index; S.frame1[e] = keyframes[image_matches[e].index1].index; }
+    image_matches = filter_image_matches_by_residual(image_matches, residuals, thresh_rad);
+    if (image_matches.empty()) { std::cout << "error: no image match survived the residual cut\n"; if (summary) *summary = S; return false; }
+    find_largest_connected_component(keyframes, image_matches, rotations);                // the cut may have split the graph
+    S.edges_kept = image_matches.size(); S.cameras_kept = keyframes.size();
+    if (summary) *summary = S;
+    // run_optimization (:1160-1188) from the L1 rotations on the kept matches
+    const int nk = (int)keyframes.size(), Ek = (int)image_matches.size();
+    std::vector<int32_t> k0(Ek), k1(Ek); std::vector<double> relk((size_t)9 * Ek), rot((size_t)9 * nk);
+    for (int e = 0; e < Ek; e++) { k0[e] = image_matches[e].index0; k1[e] = image_matches[e].index1; for (int k = 0; k < 9; k++) relk[9 * (size_t)e + k] = image_matches[e].R[k]; }
+    for (int i = 0; i < nk; i++) for (int k = 0; k < 9; k++) rot[9 * (size_t)i + k] = rotations[i][k];
+    ssfm_ba_summary B;
+    if (ssfm_posegraph_focal_solve(ctx, nk, rot.data(), Ek, k0.data(), k1.data(), relk.data(), &best_focal, min_focal, max_focal, nullptr, &B) != SSFM_OK
+        || B.termination == SSFM_FAILURE) { std::cout << "error: ceres failed.\n"; return false; }
+    for (int i = 0; i < nk; i++) for (int k = 0; k < 9; k++) rotations[i][k] = rot[9 * (size_t)i + k];
+    std::cout << "after optimization: " << best_focal << "\n";
+    return true;
+}
+
 }  // namespace sphericalsfm

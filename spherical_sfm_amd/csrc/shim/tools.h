@@ -147,4 +147,26 @@ bool find_best_focal_length_random(ssfm_ctx* ctx, int num_cameras, std::vector<I
                                    double focal_guess, double min_focal, double max_focal, int num_trials, std::vector<Mat3>& rotations,
                                    double& best_focal, unsigned seed = 0, const char* costs_path = "costs.txt");
 
+// find_best_focal_length_random on a view graph whose matches may carry wrong rotations (ssfm_focal_search_l1; DESIGN.md 4, "Robust focal search"):
+//   1. the trial focals are drawn as find_best_focal_length_random draws them (the same seed gives the same focals);
+//   2. ssfm_focal_search_l1 from camera 0 with its defaults: one L1 solve per trial, the trial with the smallest sum of residuals wins; costs_path gets
+//      "%d %lf %lf %lf": trial, focal, the sum, get_cost at the L1 rotations;
+//   3. the matches take their rotations at the found focal, and initialize_rotations_l1 (defaults: 30 iterations) gives converged residuals there --
+//      the search stops at 10 iterations, where the weights have not settled;
+//   4. filter_image_matches_by_residual(thresh_rad), then find_largest_connected_component with the rotations carried along and re-gauged: keyframes and
+//      image_matches shrink as in the calibrated driver with -rotinit l1;
+//   5. ssfm_posegraph_focal_solve from those rotations on the kept matches, inside [min_focal, max_focal].
+// The cut is applied only at the found focal: at a focal that is still off, clean loops do not close and a 2 degree cut would drop clean matches.
+// summary->frame0 / frame1 / residual list every match that entered step 3 (Keyframe::index of its two cameras, radians, -1 = not used).
+// Returns false on an error of the library or when no match survives the cut.  find_best_focal_length_random itself is untouched.
+struct FocalL1Summary {
+    size_t edges_in = 0, edges_kept = 0, cameras_in = 0, cameras_kept = 0;
+    int best_trial = 0; double focal_search = 0.0, search_cost = 0.0, search_kernel_ms = 0.0;
+    ssfm_rot_l1_summary l1{};
+    std::vector<int> frame0, frame1; std::vector<double> residual;
+};
+bool find_best_focal_length_random_l1(ssfm_ctx* ctx, std::vector<Keyframe>& keyframes, std::vector<ImageMatch>& image_matches, bool inward, double focal_guess,
+                                      double min_focal, double max_focal, int num_trials, std::vector<Mat3>& rotations, double& best_focal, unsigned seed = 0,
+                                      const char* costs_path = "costs.txt", double thresh_rad = 2.0 * 3.14159265358979323846 / 180.0, FocalL1Summary* summary = nullptr);
+
 }  // namespace sphericalsfm

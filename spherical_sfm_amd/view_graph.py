@@ -1,4 +1,4 @@
-"""Python host side of the view-graph calls (include/ssfm.h: ssfm_triplet_filter, ssfm_view_graph_tree, ssfm_focal_search_graph): what the pipeline needs when
+"""Python host side of the view-graph calls (include/ssfm.h: ssfm_triplet_filter, ssfm_view_graph_tree, ssfm_focal_search_graph, ssfm_rot_l1_init, ssfm_focal_search_l1): what the pipeline needs when
 the file order of the images is not their capture order, so that any pair (a, b) may carry a relative rotation and no chain (k-1, k) exists.
 
 Rotations are (n,3,3) arrays indexed R[i,j]; edge e = (index0[e], index1[e]) carries R_e with R_index1 = R_e R_index0."""
@@ -86,3 +86,32 @@ def focal_search_graph(ctx, num_cameras, index0, index1, rel_rotations, focal_gu
                                                   relb.ctypes.data_as(c_double_p)), ctx._p)
     out = (costs, best.value, np.transpose(rot.reshape(-1, 3, 3), (0, 2, 1)).copy())
     return out + (np.transpose(relb.reshape(-1, 3, 3), (0, 2, 1)).copy(),) if return_matches else out
+
+
+def focal_search_l1(ctx, num_cameras, index0, index1, rel_rotations, focal_guess, focals, inward=False, root=0, return_matches=False, **options):
+    """The robust focal search (ssfm_focal_search_l1): per trial focal the matches are re-derived as in focal_search_graph, the rotations are solved by the L1
+    iteration of initialize_rotations_l1 from the tree chain, and the trial is judged by the sum of the residuals |v_e| -> (costs (T,), best, rotations (n,3,3)
+    of the best trial, info).  info: get_costs (T,) (focal_search_graph's cost at the L1 rotations), iterations (T,), residual (E,) at the best trial in radians
+    (-1 for an edge that is not used), kernel_ms and, with return_matches, matches (E,3,3) at the best focal.
+    options: those of initialize_rotations_l1; the default of max_iterations is 10 here."""
+    L = _lib.lib()
+    n = int(num_cameras)
+    i0, i1, rel = _edges(index0, index1, rel_rotations) if len(index0) else (np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0))
+    E = len(i0)
+    o = _lib.RotL1OptionsC(); L.ssfm_focal_l1_default_options(C.byref(o))
+    for k, v in options.items():
+        if k not in dict(o._fields_):
+            raise TypeError(f"focal_search_l1: unknown option {k!r}")
+        setattr(o, k, v)
+    fv = np.ascontiguousarray(focals, np.float64); T = len(fv)
+    costs = np.zeros(max(T, 1)); gc = np.zeros(max(T, 1)); its = np.zeros(max(T, 1), np.int32); best = C.c_int32(0); ms = C.c_double(0.0)
+    rot = np.zeros(9 * max(n, 1)); relb = np.zeros(9 * max(E, 1)); res = np.zeros(max(E, 1))
+    p = ctx._p if ctx is not None else None
+    _lib.check(L.ssfm_focal_search_l1(p, n, E, i0.ctypes.data_as(c_i32_p), i1.ctypes.data_as(c_i32_p), rel.ctypes.data_as(c_double_p), int(bool(inward)),
+                                      float(focal_guess), T, fv.ctypes.data_as(c_double_p), int(root), C.byref(o), costs.ctypes.data_as(c_double_p),
+                                      gc.ctypes.data_as(c_double_p), its.ctypes.data_as(c_i32_p), C.byref(best), rot.ctypes.data_as(c_double_p),
+                                      relb.ctypes.data_as(c_double_p), res.ctypes.data_as(c_double_p), C.byref(ms)), p)
+    info = dict(get_costs=gc[:T].copy(), iterations=its[:T].copy(), residual=res[:E].copy(), kernel_ms=ms.value)
+    if return_matches:
+        info["matches"] = np.transpose(relb[:9 * E].reshape(-1, 3, 3), (0, 2, 1)).copy()
+    return costs[:T].copy(), best.value, np.transpose(rot[:9 * n].reshape(-1, 3, 3), (0, 2, 1)).copy(), info
