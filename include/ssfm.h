@@ -696,6 +696,51 @@ int ssfm_build_tracks(int32_t num_keyframes, const int32_t* feat_ptr, const doub
                       double centerx, double centery, int32_t merge, int32_t* tracks, int32_t* num_points, uint8_t* point_alive,
                       int64_t* num_observations, int32_t* obs_cam, int32_t* obs_pt, double* obs_xy);
 
+/* ---- feature tracks on the device: the track pass of build_sfm (merge = true) as connected components --------------------------------
+ * ssfm_build_tracks_device: the inputs of ssfm_build_tracks, all host pointers.  A global feature id is feat_ptr[k] + local index;
+ *   total = feat_ptr[num_keyframes].
+ *   Tracks.  tracks [total]: -1 for a feature that no match names; for every other feature the id of its connected component in the graph
+ *     whose edges are the matches.
+ *   Canonical ids.  The components are numbered 0 .. P-1 in ascending order of their smallest global feature id; *num_points = P; there are
+ *     no dead ids.
+ *   Observations.  Every (camera, track) pair that holds at least one feature gets one observation: that of the feature with the smallest
+ *     index among them.  Its pixel is feat_xy - (centerx, centery) in double: one subtraction, bit-equal to the host's.
+ *   Output order.  Observations come out in ascending global feature id of the winning feature.  obs_cam, obs_pt and obs_feat (the local
+ *     index of the winning feature) hold up to `total` entries, obs_xy 2 * total; the four may be NULL together, to count only.
+ *     *num_observations is always written.
+ *   Conflicts.  point_conflict (capacity `total`, may be NULL): 1 for a track that holds two or more features of one frame -- such a track is
+ *     inconsistent and the caller may drop it -- 0 otherwise; P entries are written.
+ *   Order independence.  The result does not depend on the order of the match sets, on the order of the matches inside a set (ascending
+ *     m_f0 is not required here), on repeated matches or on the run: repeats are bit-identical.  A component's root is its smallest member
+ *     whatever the schedule of the device, and everything else is a function of the roots.
+ *   A match set with index0 == index1 is accepted: its two features share a frame, so the track is flagged in point_conflict.  A match of a
+ *   feature with itself makes a track of one feature.
+ *   Four departures from ssfm_build_tracks:
+ *     the ids are canonical, not the AddPoint sequence (which issues an id per track ever started and leaves the merged ones dead);
+ *     where a track holds two features of one frame the observation is that of the smallest feature index, not of the last write;
+ *     the observations are ordered by winning feature, not camera-major / point-ascending;
+ *     there is no merge = 0 form: that mode is the order-dependent bookkeeping itself.
+ *   Where the two calls agree, on every input: the partition of the features into tracks, the set of (camera, track) observation keys after
+ *   relabelling, and the pixel of every key that holds one feature.
+ *   SSFM_ERR_INVALID before anything is launched and before the context is looked at, the message prefixed "ssfm_build_tracks_device": a NULL
+ *   feat_ptr / tracks / num_points / num_observations, some but not all of the four observation arrays, a NULL ms_index0 / ms_index1 / ms_ptr
+ *   with num_match_sets > 0 or num_match_sets < 0, num_keyframes <= 0, feat_ptr[0] != 0, a descending feat_ptr, more than 2^30 features,
+ *   a NULL feat_xy where observations are asked for, ms_ptr[0] != 0, a descending ms_ptr, a NULL m_f0 / m_f1 with matches, a frame index out
+ *   of range (in this order); then a NULL context ("ctx is null") or one with a communicator (the call is single-GPU).  A feature index
+ *   outside its frame is caught by a flag raised in the first kernel: SSFM_ERR_INVALID, "feature index out of range", no output is promised,
+ *   the context stays usable.  num_match_sets = 0 and empty sets are valid: all -1, zero points, zero observations.
+ *   Transfers: 8 bytes per match up; 4 bytes per feature, 1 per point and 8 per observation down (the camera, the local index and the pixel
+ *   of an observation follow from its global feature id on the host).  The scratch buffers and the pinned staging are kept in the context and
+ *   grown on demand.
+ * ssfm_tracks_last_kernel_ms: device time between the first and the last launch of the context's last ssfm_build_tracks_device call (one
+ *   hipEvent pair; 0 when the call had nothing to launch).  -1 on NULL arguments. */
+int ssfm_build_tracks_device(ssfm_ctx* ctx, int32_t num_keyframes, const int32_t* feat_ptr, const double* feat_xy,
+                             int32_t num_match_sets, const int32_t* ms_index0, const int32_t* ms_index1, const int32_t* ms_ptr,
+                             const int32_t* m_f0, const int32_t* m_f1, double centerx, double centery,
+                             int32_t* tracks, int32_t* num_points, uint8_t* point_conflict, int64_t* num_observations,
+                             int32_t* obs_cam, int32_t* obs_pt, int32_t* obs_feat, double* obs_xy);
+int ssfm_tracks_last_kernel_ms(ssfm_ctx* ctx, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,7 @@ DECLARED_SYMBOLS = [
     "ssfm_rot_l1_default_options", "ssfm_rot_l1_init",
     "ssfm_focal_l1_default_options", "ssfm_focal_search_l1",
     "ssfm_anms_default_options", "ssfm_anms_batch", "ssfm_anms_batch_host", "ssfm_anms_last_kernel_ms",
+    "ssfm_build_tracks_device", "ssfm_tracks_last_kernel_ms",
 ]
 
 
@@ -251,6 +252,10 @@ def lib():
     L.ssfm_anms_batch.argtypes = [vp, C.c_int32, c_i32_p, c_float_p, c_float_p, c_i32_p, C.POINTER(AnmsOptionsC), c_i32_p, c_i32_p, c_double_p]; L.ssfm_anms_batch.restype = C.c_int
     L.ssfm_anms_batch_host.argtypes = [C.c_int32, c_i32_p, c_float_p, c_float_p, c_i32_p, C.c_int32, c_i32_p, c_i32_p, c_double_p]; L.ssfm_anms_batch_host.restype = C.c_int
     L.ssfm_anms_last_kernel_ms.argtypes = [vp, c_double_p]; L.ssfm_anms_last_kernel_ms.restype = C.c_int
+    L.ssfm_build_tracks_device.argtypes = [vp, C.c_int32, c_i32_p, c_double_p, C.c_int32, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, C.c_double, C.c_double,
+                                           c_i32_p, c_i32_p, c_u8_p, c_i64_p, c_i32_p, c_i32_p, c_i32_p, c_double_p]
+    L.ssfm_build_tracks_device.restype = C.c_int
+    L.ssfm_tracks_last_kernel_ms.argtypes = [vp, c_double_p]; L.ssfm_tracks_last_kernel_ms.restype = C.c_int
     _LIB = L
     return L
 

@@ -13,7 +13,8 @@
 // exceeds -rotinitthresh degrees (default 2) are dropped, find_largest_connected_component runs once more, and refine_rotations starts from the L1 rotations of the
 // cameras that are left; rotinit.txt lists every pair with its residual.  One wrong match on a tree edge no longer rotates a whole subtree, and the gross outliers no longer bias the averaging.
 //   run_spherical_sfm -intrinsics <file: focal cx cy> -output <dir with the feature tracks> [-match | -pairwise] [-inward] [-width W -height H]
-//                     [-viewgraph [-tripletorder reference|composed] [-rotinit tree|l1] [-rotinitthresh DEG]]
+//                     [-viewgraph [-tripletorder reference|composed] [-rotinit tree|l1] [-rotinitthresh DEG]] [-devicetracks]
+// -devicetracks: build_sfm's track pass runs on the device (ssfm_build_tracks_device: connected components, canonical point ids).  Without it nothing changes.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -24,7 +25,7 @@ using namespace sphericalsfm;
 
 int main(int argc, char** argv) {
     std::string intrinsics_path, output; bool inward = false, pairwise = false, match_mode = false, viewgraph = false; int triplet_order = SSFM_TRIPLET_ORDER_REFERENCE, width = 1920, height = 1080, mininliers = 100; double inlierthresh = 2.0;
-    bool rotinit_l1 = false; double rotinit_thresh_deg = 2.0;
+    bool rotinit_l1 = false, device_tracks = false; double rotinit_thresh_deg = 2.0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "-intrinsics" && i + 1 < argc) intrinsics_path = argv[++i];
@@ -32,6 +33,7 @@ int main(int argc, char** argv) {
         else if (a == "-width" && i + 1 < argc) width = std::atoi(argv[++i]);
         else if (a == "-height" && i + 1 < argc) height = std::atoi(argv[++i]);
         else if (a == "-inward") inward = true;
+        else if (a == "-devicetracks") device_tracks = true;                // build_sfm's track pass on the device (ssfm_build_tracks_device); default: the host pass
         else if (a == "-pairwise") pairwise = true;                         // matches.dat holds raw matches: run estimate_pairwise (GPU RANSAC) first
         else if (a == "-match") match_mode = true;                          // no matches.dat: features -> verified image matches on the device
         else if (a == "-inlierthresh" && i + 1 < argc) inlierthresh = std::atof(argv[++i]);
@@ -115,7 +117,7 @@ int main(int argc, char** argv) {
     const double rot_cost = refine_rotations(sfm.GetContext(), (int)keyframes.size(), image_matches, rotations);
 
     std::cout << "building sfm\n";
-    build_sfm(keyframes, image_matches, rotations, sfm, true, true, inward);
+    build_sfm(keyframes, image_matches, rotations, sfm, true, true, inward, 0, device_tracks);
     sfm.WritePointsOBJ(output + "/points-pre-spherical-ba.obj");
     sfm.WriteCameraCentersOBJ(output + "/cameras-pre-spherical-ba.obj");
 

@@ -15,7 +15,8 @@
 // three-point estimator: with -match in one device call from the feature tables (estimate_pairwise_five_point_from_features: the match lists stay on the
 // device), without it on the matches of matches.dat, whose rotations it replaces.
 //   run_spherical_sfm_uncalib -output <dir with keyframes.txt, features.dat, matches.dat> -width W -height H [-generalba] [-inward]
-//                             [-match] [-fivepoint] [-inlierthresh T] [-mininliers N] [-viewgraph [-rotinit tree|l1] [-rotinitthresh DEG]]
+//                             [-match] [-fivepoint] [-inlierthresh T] [-mininliers N] [-viewgraph [-rotinit tree|l1] [-rotinitthresh DEG]] [-devicetracks]
+// -devicetracks: build_sfm's track pass runs on the device (ssfm_build_tracks_device: connected components, canonical point ids).  Without it nothing changes.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -25,7 +26,7 @@ using namespace sphericalsfm;
 
 int main(int argc, char** argv) {
     std::string output; bool inward = false, generalba = false, match_mode = false, viewgraph = false, fivepoint = false; int width = 0, height = 0, num_trials = 1024, mininliers = 100; unsigned seed = 0; double inlierthresh = 2.0;
-    bool rotinit_l1 = false; double rotinit_thresh_deg = 2.0;
+    bool rotinit_l1 = false, device_tracks = false; double rotinit_thresh_deg = 2.0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "-output" && i + 1 < argc) output = argv[++i];
@@ -34,6 +35,7 @@ int main(int argc, char** argv) {
         else if (a == "-trials" && i + 1 < argc) num_trials = std::atoi(argv[++i]);
         else if (a == "-seed" && i + 1 < argc) seed = (unsigned)std::atoi(argv[++i]);
         else if (a == "-inward") inward = true;
+        else if (a == "-devicetracks") device_tracks = true;                // build_sfm's track pass on the device (ssfm_build_tracks_device); default: the host pass
         else if (a == "-generalba") generalba = true;
         else if (a == "-match") match_mode = true;
         else if (a == "-fivepoint") fivepoint = true;
@@ -100,7 +102,7 @@ int main(int argc, char** argv) {
 
     std::cout << "building sfm\n";
     SfM sfm(intrinsics);
-    build_sfm(keyframes, image_matches, rotations, sfm, true, true, inward);
+    build_sfm(keyframes, image_matches, rotations, sfm, true, true, inward, 0, device_tracks);
     sfm.SetFocalFixed(false);
     sfm.WriteCOLMAP(output + "/sparse-pre-spherical-ba", width, height);
     sfm.WritePointsOBJ(output + "/points-pre-spherical-ba.obj");

@@ -356,7 +356,7 @@ double refine_rotations(ssfm_ctx* ctx, int num_cameras, const std::vector<ImageM
 }
 
 void build_sfm(std::vector<Keyframe>& keyframes, const std::vector<ImageMatch>& image_matches, const std::vector<Mat3>& rotations, SfM& sfm,
-               bool spherical, bool merge, bool inward, int fix_camera) {
+               bool spherical, bool merge, bool inward, int fix_camera, bool device_tracks) {
     std::cout << "building tracks\n";
     const int nk = (int)keyframes.size();
     std::vector<int32_t> feat_ptr(nk + 1, 0);
@@ -371,7 +371,9 @@ void build_sfm(std::vector<Keyframe>& keyframes, const std::vector<ImageMatch>& 
         ms_ptr.push_back((int32_t)f0.size());
     }
     const size_t nm = f0.size();
-    std::vector<int32_t> tracks(feat_ptr[nk]), ocam(2 * nm + 1), opt(2 * nm + 1); std::vector<uint8_t> alive(nm + 1); std::vector<double> oxy(4 * nm + 2);
+    if (device_tracks && !merge) { std::cout << "device tracks need merge = true: the host track pass runs\n"; device_tracks = false; }
+    const size_t nobs_cap = device_tracks ? (size_t)feat_ptr[nk] + 1 : 2 * nm + 1;
+    std::vector<int32_t> tracks(feat_ptr[nk]), ocam(nobs_cap), opt(nobs_cap); std::vector<uint8_t> alive(device_tracks ? 1 : nm + 1); std::vector<double> oxy(2 * nobs_cap);
     int32_t npts = 0; int64_t nobs = 0;
     std::cout << "adding cameras\n";
     for (int index = 0; index < nk; index++) {
@@ -383,11 +385,21 @@ void build_sfm(std::vector<Keyframe>& keyframes, const std::vector<ImageMatch>& 
         sfm.SetTranslationFixed(camera, spherical ? true : (index == fix_camera));
     }
     std::cout << "adding tracks\nnumber of keyframes is " << nk << "\n";
-    ssfm_build_tracks(nk, feat_ptr.data(), feat_xy.data(), (int32_t)image_matches.size(), ms0.data(), ms1.data(), ms_ptr.data(), f0.data(), f1.data(),
-                      sfm.GetIntrinsics().centerx, sfm.GetIntrinsics().centery, merge ? 1 : 0, tracks.data(), &npts, alive.data(), &nobs, ocam.data(), opt.data(), oxy.data());
+    if (device_tracks) {                                                             // connected components with canonical ids: every id is alive
+        std::vector<int32_t> ofeat(nobs_cap);
+        ssfm_ctx* ctx = sfm.GetContext();
+        if (ssfm_build_tracks_device(ctx, nk, feat_ptr.data(), feat_xy.data(), (int32_t)image_matches.size(), ms0.data(), ms1.data(), ms_ptr.data(), f0.data(), f1.data(),
+                                     sfm.GetIntrinsics().centerx, sfm.GetIntrinsics().centery, tracks.data(), &npts, nullptr, &nobs, ocam.data(), opt.data(), ofeat.data(),
+                                     oxy.data()) != SSFM_OK) {
+            std::cout << "error: " << ssfm_last_error(ctx) << "\n"; std::exit(1);
+        }
+        std::cout << "device tracks: " << npts << " points, " << nobs << " observations\n";
+    }
+    else ssfm_build_tracks(nk, feat_ptr.data(), feat_xy.data(), (int32_t)image_matches.size(), ms0.data(), ms1.data(), ms_ptr.data(), f0.data(), f1.data(),
+                           sfm.GetIntrinsics().centerx, sfm.GetIntrinsics().centery, merge ? 1 : 0, tracks.data(), &npts, alive.data(), &nobs, ocam.data(), opt.data(), oxy.data());
     for (int i = 0; i < nk; i++) keyframes[i].features.tracks.assign(tracks.begin() + feat_ptr[i], tracks.begin() + feat_ptr[i + 1]);
     for (int j = 0; j < npts; j++) { const int p = sfm.AddPoint(Point(0, 0, 0)); sfm.SetPointFixed(p, false); }
-    for (int j = 0; j < npts; j++) if (!alive[j]) sfm.RemovePoint(j);                    // points consumed by MergePoint
+    if (!device_tracks) for (int j = 0; j < npts; j++) if (!alive[j]) sfm.RemovePoint(j);   // points consumed by MergePoint
     for (int64_t o = 0; o < nobs; o++) sfm.AddObservation(ocam[o], opt[o], Observation(oxy[2 * o], oxy[2 * o + 1]));
     std::cout << "retriangulating...\n";
     sfm.Retriangulate();

@@ -107,7 +107,10 @@ void initialize_rotations_sequential(int num_cameras, const std::vector<ImageMat
 double refine_rotations(ssfm_ctx* ctx, int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations); // tools.cpp:851-860
 // tools.cpp:862-955: tracks (ssfm_build_tracks, ids bit-exact with the reference's AddPoint sequence), cameras, observations, Retriangulate
 void build_sfm(std::vector<Keyframe>& keyframes, const std::vector<ImageMatch>& image_matches, const std::vector<Mat3>& rotations, SfM& sfm,
-               bool spherical, bool merge, bool inward, int fix_camera = 0);
+               bool spherical, bool merge, bool inward, int fix_camera = 0, bool device_tracks = false);
+// device_tracks (with merge): the tracks come from ssfm_build_tracks_device on sfm.GetContext() -- connected components of the matches with canonical ids, P points
+// added and none removed, the observations added as returned (include/ssfm.h states where that call and ssfm_build_tracks agree).  With merge == false the host
+// pass runs and a line on stdout says so.  Default false: the host pass, unchanged.
 
 // filter_image_matches (spherical_sfm_tools.cpp:1031-1082) over ssfm_triplet_filter: every ordered triple of matches (i, j, k) with i = (a, b), j = (b, c), k = (a, c)
 // is a triplet; a triplet whose rotation error is below err_thresh_rad marks its three matches good; the good matches come back in list order.  order: which product

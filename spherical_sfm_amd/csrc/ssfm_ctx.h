@@ -30,6 +30,9 @@ struct ssfm_ctx {
     double match_kernel_ms = 0.0;       // the same for the last ssfm_match_pairs call, ssfm_match_last_kernel_ms
     double front_kernel_ms = 0.0;       // the same for the last ssfm_pairwise_from_features / ssfm_pairwise5_from_features call (its matching + its RANSAC slabs, hand-over kernels included)
     double anms_kernel_ms = 0.0;        // the same for the last ssfm_anms_batch call (one event pair round its launches), ssfm_anms_last_kernel_ms
+    double tracks_kernel_ms = 0.0;      // the same for the last ssfm_build_tracks_device call, ssfm_tracks_last_kernel_ms
+    void* tracks_dev = nullptr; size_t tracks_dev_bytes = 0;     // device scratch of ssfm_build_tracks_device (tracks_device.hip), grow-only
+    void* tracks_pin = nullptr; size_t tracks_pin_bytes = 0;     // its pinned staging, grow-only
 };
 
 namespace ssfm {
