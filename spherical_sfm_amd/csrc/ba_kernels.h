@@ -190,6 +190,25 @@ __device__ __forceinline__ double obs_cost(double f, const double* t, const doub
     double rho0, rho1; robust_loss(loss, la, r0 * r0 + r1 * r1, rho0, rho1);
     return 0.5 * rho0;
 }
+// The robustified cost 0.5 rho(s) of the observations of ONE lane, of which only the sum is used.  Loss types 0 and 2 add 0.5 rho(s) per observation (robust_loss's
+// arithmetic).  Type 1 (Cauchy, rho = b log(1 + s/b)) multiplies the factor 1 + s (1/b) into a LogProd (ssfm_math.h) and takes ONE log per flush: cost_flush before the
+// lane's sum is used, and cost_room(k) in front of a batch of k <= LOGPROD_MAX calls of cost_add, which flushes when the product has no room for k more factors.
+// Which factors share a product follows from the lane's own sequence of calls alone (an observation that is switched off is the factor 1 and counts), so it is a
+// function of the plan and never of scheduling.
+struct CostAcc {
+    double sum = 0.0, ib; LogProd lp; int n = 0;
+    __device__ __forceinline__ CostAcc(double la) : ib(1.0 / (la * la)) {}                 // wave-uniform: the one division of the kernel
+};
+__device__ __forceinline__ void cost_flush(CostAcc& c, int loss, double la) { if (loss == 1) { c.sum += 0.5 * (la * la) * logprod_flush(c.lp); c.n = 0; } }
+__device__ __forceinline__ void cost_room(CostAcc& c, int loss, double la, int k) { if (c.n + k > LOGPROD_MAX) cost_flush(c, loss, la); }
+__device__ __forceinline__ void cost_add(CostAcc& c, int loss, double la, double s, bool on) {
+    if (loss == 1) { logprod_mul(c.lp, on ? 1.0 + s * c.ib : 1.0); c.n++; }
+    else { double rho0, rho1; robust_loss(loss, la, s, rho0, rho1); c.sum += on ? 0.5 * rho0 : 0.0; }
+}
+__device__ __forceinline__ void obs_cost_acc(double f, const double* t, const double* R, const double* X, double ox, double oy, int loss, double la, CostAcc& c, bool on) {
+    double xp, yp, iz, r0, r1; project(f, t, R, X, ox, oy, xp, yp, iz, r0, r1);
+    cost_add(c, loss, la, r0 * r0 + r1 * r1, on);
+}
 template <bool NEED_T>
 __device__ __forceinline__ void lin_obs(double f, const double* t, const double* rot, const double* X, double ox, double oy,
                                         int loss, double la, ObsLin& L) {
@@ -221,18 +240,39 @@ __device__ __forceinline__ void lin_obs(double f, const double* t, const double*
     }
 }
 // point-side view of the same linearisation (no camera blocks, R only): residual, focal column, point block
-struct ObsPoint { double r[2], Jf[2], Jp[2][3], half_rho; };
+// (the observation's cost goes into the lane's CostAcc; on = false: an observation that is recomputed for its loads' sake and does not count)
+struct ObsPoint { double r[2], Jf[2], Jp[2][3]; };
 __device__ __forceinline__ void lin_obs_point(double f, const double* t, const double* R, const double* X, double ox, double oy, int loss, double la,
-                                              ObsPoint& L) {
+                                              ObsPoint& L, CostAcc& cost, bool on) {
     double xp, yp, iz, r0, r1; project(f, t, R, X, ox, oy, xp, yp, iz, r0, r1);
-    double rho0, rho1; robust_loss(loss, la, r0 * r0 + r1 * r1, rho0, rho1);      // only rho(s) is used from here: dead code where the cost is not
+    cost_add(cost, loss, la, r0 * r0 + r1 * r1, on);
     const double sr = loss_sqrt_weight(loss, la, r0 * r0 + r1 * r1);
-    L.half_rho = 0.5 * rho0;
     L.r[0] = sr * r0; L.r[1] = sr * r1;
     L.Jf[0] = sr * xp; L.Jf[1] = sr * yp;
     const double a = sr * f * iz, a02 = -a * xp, a12 = -a * yp;
 #pragma unroll
     for (int k = 0; k < 3; k++) { L.Jp[0][k] = a * R[k] + a02 * R[6 + k]; L.Jp[1][k] = a * R[3 + k] + a12 * R[6 + k]; }
+}
+// the back substitution's view: residual, focal column and point block as lin_obs gives them, and in place of the camera blocks Jt, Jr their PRODUCT with the camera's
+// step, which is all the model residual needs:  with Jt = A and Jr = -(A Rd) [X]x M (lin_obs),  Jt dt + Jr dr = A (dt - Rd (X x q)),  q = M dr  (one 3-vector per camera,
+// formed once per task).  HAS_T = false (3-dof cameras): no translation term.  rot = [R | Rd | M] as in lin_obs; M is not read.
+struct ObsModel { double r[2], Jf[2], Jp[2][3], mc[2]; };
+template <bool HAS_T>
+__device__ __forceinline__ void lin_obs_model(double f, const double* t, const double* rot, const double* X, double ox, double oy, int loss, double la,
+                                              const double* dt, const double* q, ObsModel& L) {
+    const double* R = rot; const double* Rd = rot + 9;
+    double xp, yp, iz, r0, r1; project(f, t, R, X, ox, oy, xp, yp, iz, r0, r1);
+    const double sr = loss_sqrt_weight(loss, la, r0 * r0 + r1 * r1);
+    L.r[0] = sr * r0; L.r[1] = sr * r1;
+    L.Jf[0] = sr * xp; L.Jf[1] = sr * yp;
+    const double a = sr * f * iz, a02 = -a * xp, a12 = -a * yp;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { L.Jp[0][k] = a * R[k] + a02 * R[6 + k]; L.Jp[1][k] = a * R[3 + k] + a12 * R[6 + k]; }
+    const double v[3] = {X[1] * q[2] - X[2] * q[1], X[2] * q[0] - X[0] * q[2], X[0] * q[1] - X[1] * q[0]};
+    double e[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) e[k] = (HAS_T ? dt[k] : 0.0) - (Rd[3 * k] * v[0] + Rd[3 * k + 1] * v[1] + Rd[3 * k + 2] * v[2]);
+    L.mc[0] = a * e[0] + a02 * e[2]; L.mc[1] = a * e[1] + a12 * e[2];
 }
 // scaled camera block Jc[2][DC] of an observation (DC=6: [t r], DC=3: r only)
 template <int DC>
@@ -374,6 +414,7 @@ k_point_lin(const double* __restrict__ cam, const double* __restrict__ rot, cons
         const double sp[3] = {scale_pt[3 * p], scale_pt[3 * p + 1], scale_pt[3 * p + 2]};
         const double f = focal[0], sf = scale_f[0];
         double V[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0}, wf[3] = {0, 0, 0};
+        CostAcc cost(la);
         // observations in groups of OBS_UNROLL: indices first, then every camera's [t | R], then the arithmetic, so that the
         // dependent gathers of a group are in flight together (a point has 3-10 observations; lanes beyond the list recompute
         // the last one with zero weight)
@@ -395,11 +436,11 @@ k_point_lin(const double* __restrict__ cam, const double* __restrict__ rot, cons
             // the indices of the next group travel with this group's camera tables: one dependent round trip per group
 #pragma unroll
             for (int u = 0; u < OBS_UNROLL; u++) { const int jj = min(jb + OBS_UNROLL + u, je - 1); cn[u] = obs_cam[jj]; on[u] = obs_xy[jj]; }
+            cost_room(cost, loss, la, OBS_UNROLL);
 #pragma unroll
             for (int u = 0; u < OBS_UNROLL; u++) {
                 const double wgt = (jb + u < je) ? 1.0 : 0.0;
-                ObsPoint L; lin_obs_point(f, tR[u], tR[u] + 3, X, oo[u].x, oo[u].y, loss, la, L);
-                acc[0] += wgt * L.half_rho;
+                ObsPoint L; lin_obs_point(f, tR[u], tR[u] + 3, X, oo[u].x, oo[u].y, loss, la, L, cost, jb + u < je);
 #pragma unroll
                 for (int a = 0; a < 2; a++) {
                     const double j0 = L.Jp[a][0] * sp[0] * wgt, j1 = L.Jp[a][1] * sp[1] * wgt, j2 = L.Jp[a][2] * sp[2] * wgt, jf = L.Jf[a] * sf * wgt;
@@ -410,11 +451,13 @@ k_point_lin(const double* __restrict__ cam, const double* __restrict__ rot, cons
                 }
             }
         }
+        cost_flush(cost, loss, la); acc[0] = cost.sum;
         if (sp[0] > 0.0) {
             gmax = fmax(fabs(g[0] / sp[0]), fmax(fabs(g[1] / sp[1]), fabs(g[2] / sp[2])));
-            V[0] += fmin(fmax(V[0], min_diag), max_diag) / radius;
-            V[3] += fmin(fmax(V[3], min_diag), max_diag) / radius;
-            V[5] += fmin(fmax(V[5], min_diag), max_diag) / radius;
+            const double irad = 1.0 / radius;                       // (the fused prologue of schur_gram_task damps with the same reciprocal: the two records agree bit for bit)
+            V[0] += fmin(fmax(V[0], min_diag), max_diag) * irad;
+            V[3] += fmin(fmax(V[3], min_diag), max_diag) * irad;
+            V[5] += fmin(fmax(V[5], min_diag), max_diag) * irad;
         } else { V[0] = V[3] = V[5] = 1.0; }   // constant point: identity block, zero coupling
         double Vi[6]; sym3_inverse(V, Vi);
         const double u0 = wf[0] * Vi[0] + wf[1] * Vi[1] + wf[2] * Vi[2];
@@ -739,12 +782,28 @@ __device__ __forceinline__ void gram_gather(const double* __restrict__ A, const 
 // FUSE (every point of the problem sits in a signature group): the task also does k_point_lin's work for its own points, ONCE, in a prologue in front of the sub-chunk
 // loop -- one lane per point in rounds of 64, the K observations of the point in k_point_lin's order and arithmetic against the camera records the task has just staged
 // in LDS (a wave-uniform record address: an LDS broadcast where k_point_lin makes dependent global gathers), damping, sym3_inverse, the 12-double record PS and g_p to
-// global memory for the back substitution.  The sub-chunk loop then reads PS back as the unfused kernel does (the same wave wrote it: a workgroup-scope fence, no
-// agent-scope one) and stays instruction for instruction what it was; the wave adds the five point-pass sums (cost, focal sums) and the gradient maximum to its scalar
+// global memory for the back substitution, and (round 10) the Cholesky factor of the record's scaled V^-1 to LF_out.  The sub-chunk loop then reads PS[6..] and that
+// factor back (the same wave wrote them: a workgroup-scope fence, no agent-scope one) where the unfused loop reads PS[0..] and factors per lane; the wave adds the five point-pass sums (cost, focal sums) and the gradient maximum to its scalar
 // slot at the end.  k_point_lin does not run then.  Round 5 had this work INSIDE the loop, a lane per observation: every observation linearised twice, 12 doubles folded
 // over the observation lanes per sub-chunk, all 64 lanes inverting the same eight blocks -- 2.3 x the loop's vector instructions (profiles/r09_notes.md).
 // spec (speculative launch behind k_publish, like k_point_lin's): [go, radius] as decided on the device.
-struct GramFuse { const double* scale_pt; double radius, min_diag, max_diag; double* PS_out; double* gp_out; double* scal; const double* spec; int emit_skip = 0; };
+// Cholesky factor (L00 L10 L20 L11 L21 L22) of the scaled V^-1 of a point record (PS[0..5]); L comes in zeroed: all zero for a fixed point, whose record is zero, and a
+// pivot that is not positive leaves the rest of the factor zero
+__device__ __forceinline__ void chol3_scaled(const double* V, double* L) {
+    if (V[0] > 0.0) {
+        const double i0 = fast_rsqrt(V[0]);
+        L[0] = V[0] * i0; L[1] = V[1] * i0; L[2] = V[2] * i0;
+        const double d1 = V[3] - L[1] * L[1];
+        if (d1 > 0.0) {
+            const double i1 = fast_rsqrt(d1);
+            L[3] = d1 * i1; L[4] = (V[4] - L[2] * L[1]) * i1;
+            const double d2 = V[5] - L[2] * L[2] - L[4] * L[4];
+            if (d2 > 0.0) L[5] = d2 * fast_rsqrt(d2);
+        }
+    }
+}
+// LF_out: 6 doubles per point, chol3_scaled of the record's V^-1 -- the prologue factors once per point what the unfused loop factors on every observation lane of every sub-chunk
+struct GramFuse { const double* scale_pt; double radius, min_diag, max_diag; double* PS_out; double* gp_out; double* scal; const double* spec; int emit_skip = 0; double* LF_out = nullptr; };
 // one wave task of k_schur_gram / k_schur_gram_any (below): the task's tile shape (NT, TI) is a template parameter, the task index an argument
 template <int DC, int NT, int TI, bool FUSE>
 __device__ __forceinline__ void
@@ -776,6 +835,8 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
     const double sf = scale_f[0];
     if constexpr (FUSE) {
         double pacc[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, pgmax = 0.0;         // cost, FJJ, FJR, FWW, FWG of this lane's points; gradient maximum
+        CostAcc cost(la);                                                // the cost of this lane's points over all rounds: one log per lane and flush
+        const double irad = 1.0 / fz_radius;                             // wave-uniform: one division for the three damping terms of every point
         // ---- the point pass of the task's points (k_point_lin), before the camera sums and the tile accumulators are alive
         constexpr int KC = ((16 * NT + (TI > 0 ? 4 : 0)) / DC < GRAM_KMAX) ? (16 * NT + (TI > 0 ? 4 : 0)) / DC : GRAM_KMAX;      // the longest camera list of this tile class
         wave_lds_handover();                                             // sCam is written
@@ -789,13 +850,13 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
             for (int k = 0; k < 3; k++) { Xp[k] = pts[3 * p + k]; sp[k] = fz.scale_pt[3 * p + k]; }
 #pragma unroll
             for (int k = 0; k < KC; k++) oo[k] = op[min(k, K - 1)];      // every observation of the point in flight at once
-            double Vd[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0}, wf[3] = {0, 0, 0}, a0 = 0.0, a1 = 0.0, a2 = 0.0;
+            double Vd[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0}, wf[3] = {0, 0, 0}, a1 = 0.0, a2 = 0.0;
+            cost_room(cost, loss, la, KC);
 #pragma unroll
             for (int k = 0; k < KC; k++)
                 if (k < K) {                                             // wave-uniform
                     const double* crec = sCam + k * GRAM_CAMREC;
-                    ObsPoint L; lin_obs_point(f, crec, crec + 6, Xp, oo[k].x, oo[k].y, loss, la, L);
-                    a0 += L.half_rho;
+                    ObsPoint L; lin_obs_point(f, crec, crec + 6, Xp, oo[k].x, oo[k].y, loss, la, L, cost, valid);
 #pragma unroll
                     for (int a = 0; a < 2; a++) {
                         const double j0 = L.Jp[a][0] * sp[0], j1 = L.Jp[a][1] * sp[1], j2 = L.Jp[a][2] * sp[2], jf = L.Jf[a] * sf;
@@ -808,30 +869,36 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
             double gm = 0.0;
             if (sp[0] > 0.0) {
                 gm = fmax(fabs(g[0] / sp[0]), fmax(fabs(g[1] / sp[1]), fabs(g[2] / sp[2])));
-                Vd[0] += fmin(fmax(Vd[0], fz.min_diag), fz.max_diag) / fz_radius;
-                Vd[3] += fmin(fmax(Vd[3], fz.min_diag), fz.max_diag) / fz_radius;
-                Vd[5] += fmin(fmax(Vd[5], fz.min_diag), fz.max_diag) / fz_radius;
+                Vd[0] += fmin(fmax(Vd[0], fz.min_diag), fz.max_diag) * irad;
+                Vd[3] += fmin(fmax(Vd[3], fz.min_diag), fz.max_diag) * irad;
+                Vd[5] += fmin(fmax(Vd[5], fz.min_diag), fz.max_diag) * irad;
             } else { Vd[0] = Vd[3] = Vd[5] = 1.0; }                       // constant point: identity block, zero coupling
             double Vi[6]; sym3_inverse(Vd, Vi);
             const double u0 = wf[0] * Vi[0] + wf[1] * Vi[1] + wf[2] * Vi[2];
             const double u1 = wf[0] * Vi[1] + wf[1] * Vi[3] + wf[2] * Vi[4];
             const double u2 = wf[0] * Vi[2] + wf[1] * Vi[4] + wf[2] * Vi[5];
             if (valid) {
-                pacc[0] += a0; pacc[1] += a1; pacc[2] += a2;
+                pacc[1] += a1; pacc[2] += a2;
                 pacc[3] += u0 * wf[0] + u1 * wf[1] + u2 * wf[2];
                 pacc[4] += u0 * g[0] + u1 * g[1] + u2 * g[2];
                 pgmax = fmax(pgmax, gm);
                 double* ps = fz.PS_out + 12 * p;                          // the record of k_point_lin: [ diag(s) V^-1 diag(s) (6) | s o (V^-1 g) (3) | s o (V^-1 w_f) (3) ]
-                ps[0] = Vi[0] * sp[0] * sp[0]; ps[1] = Vi[1] * sp[0] * sp[1]; ps[2] = Vi[2] * sp[0] * sp[2];
-                ps[3] = Vi[3] * sp[1] * sp[1]; ps[4] = Vi[4] * sp[1] * sp[2]; ps[5] = Vi[5] * sp[2] * sp[2];
+                const double Vsc[6] = {Vi[0] * sp[0] * sp[0], Vi[1] * sp[0] * sp[1], Vi[2] * sp[0] * sp[2], Vi[3] * sp[1] * sp[1], Vi[4] * sp[1] * sp[2], Vi[5] * sp[2] * sp[2]};
+#pragma unroll
+                for (int k = 0; k < 6; k++) ps[k] = Vsc[k];
                 ps[6] = sp[0] * (Vi[0] * g[0] + Vi[1] * g[1] + Vi[2] * g[2]); ps[7] = sp[1] * (Vi[1] * g[0] + Vi[3] * g[1] + Vi[4] * g[2]);
                 ps[8] = sp[2] * (Vi[2] * g[0] + Vi[4] * g[1] + Vi[5] * g[2]);
                 ps[9] = sp[0] * u0; ps[10] = sp[1] * u1; ps[11] = sp[2] * u2;
+                double Lf[6] = {0, 0, 0, 0, 0, 0}; chol3_scaled(Vsc, Lf);             // of the values that went to ps[0..5]: what the unfused loop factors after reading them back
+                double* lf = fz.LF_out + 6 * p;
+#pragma unroll
+                for (int k = 0; k < 6; k++) lf[k] = Lf[k];
 #pragma unroll
                 for (int k = 0; k < 3; k++) fz.gp_out[3 * p + k] = g[k];
             }
         }
         {                                                                // the point pass's sums and gradient maximum, one wave = one scalar slot (k_point_lin's rule); here and
+            cost_flush(cost, loss, la); pacc[0] = cost.sum;
             const double t = wave_transpose_sum(pacc);                   // not at the end of the task: twelve registers less across the sub-chunk loop
             pgmax = wave_max(pgmax);
             const int slot = wave_tr_index();
@@ -864,7 +931,8 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
     do {                                                                                                                          \
         const int q_ = min((s0_) + lp, cnt - 1);                                                                                  \
         _Pragma("unroll") for (int k = 0; k < 3; k++) X[k] = pts[3 * (size_t)(p0 + q_) + k];                                      \
-        _Pragma("unroll") for (int k = 0; k < 9; k++) V[k] = PSr[12 * (size_t)(p0 + q_) + k];                                     \
+        if (FUSE) { _Pragma("unroll") for (int k = 0; k < 6; k++) V[k] = fz.LF_out[6 * (size_t)(p0 + q_) + k]; }                  \
+        _Pragma("unroll") for (int k = FUSE ? 6 : 0; k < 9; k++) V[k] = PSr[12 * (size_t)(p0 + q_) + k];                          \
         if (focal_free) { _Pragma("unroll") for (int k = 9; k < 12; k++) V[k] = PSr[12 * (size_t)(p0 + q_) + k]; }                \
         ob = obs_xy[j00 + (size_t)q_ * K + kq];                                                                                   \
     } while (0)
@@ -877,18 +945,14 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
             const double* crec = sCam + kq * GRAM_CAMREC;
             ObsLin Lk; lin_obs<DC == 6>(f, crec, crec + 6, X, ob.x, ob.y, loss, la, Lk);
             // Cholesky factor of the scaled V^-1 (all zero for a fixed point or a lane past the end of the task: its columns of Y are zero)
-            double L00 = 0, L10 = 0, L20 = 0, L11 = 0, L21 = 0, L22 = 0;
-            if (valid && V[0] > 0.0) {
-                const double i0 = fast_rsqrt(V[0]);
-                L00 = V[0] * i0; L10 = V[1] * i0; L20 = V[2] * i0;
-                const double d1 = V[3] - L10 * L10;
-                if (d1 > 0.0) {
-                    const double i1 = fast_rsqrt(d1);
-                    L11 = d1 * i1; L21 = (V[4] - L20 * L10) * i1;
-                    const double d2 = V[5] - L20 * L20 - L21 * L21;
-                    if (d2 > 0.0) L22 = d2 * fast_rsqrt(d2);
+            double Lf[6] = {0, 0, 0, 0, 0, 0};                           // L00 L10 L20 L11 L21 L22
+            if (FUSE) {                                                  // the prologue factored once per point: V[0..5] IS the factor
+                if (valid) {
+#pragma unroll
+                    for (int k = 0; k < 6; k++) Lf[k] = V[k];
                 }
-            }
+            } else if (valid) chol3_scaled(V, Lf);
+            const double L00 = Lf[0], L10 = Lf[1], L20 = Lf[2], L11 = Lf[3], L21 = Lf[4], L22 = Lf[5];
             double Jc[2][DC]; cam_block_raw<DC>(Lk, Jc);
             double T[2][3];
 #pragma unroll
@@ -1958,12 +2022,15 @@ k_point_backsub(const double* __restrict__ cam, const double* __restrict__ rot, 
         }
         // robustified cost at the candidate (cameras, focal, this point): what a separate k_point_cost launch did
         const double fcand = focal_c[0];
+        CostAcc cost(la);
         c_nx = obs_cam[jf]; o_nx = obs_xy[jf];
         for (int j = j0 + hl; j < j1; j += LPP) {
             const int c = c_nx; const double2 o = o_nx;
             { const int jn = min(j + LPP, j1 - 1); c_nx = obs_cam[jn]; o_nx = obs_xy[jn]; }
-            acc[3] += obs_cost(fcand, cam_c + 6 * c, rot_c + 27 * c, Xc, o.x, o.y, loss, la);
+            cost_room(cost, loss, la, 1);
+            obs_cost_acc(fcand, cam_c + 6 * c, rot_c + 27 * c, Xc, o.x, o.y, loss, la, cost, true);
         }
+        cost_flush(cost, loss, la); acc[3] = cost.sum;
     }
     // per-wave fold and atomics (see k_point_lin): no barrier at the end
     static_assert(SC_STEP2_PT == SC_MODEL + 1 && SC_XN2_PT == SC_MODEL + 2 && SC_CAND_COST == SC_MODEL + 3, "the four sums are consecutive scalars");
@@ -2026,7 +2093,6 @@ k_gram_backsub2(const double* __restrict__ cam, const double* __restrict__ rot, 
                 const double* __restrict__ res_Sff, double res_tol2, double* __restrict__ res_r, double* __restrict__ res_pcg, long long* __restrict__ lacc = nullptr,
                 const int split = 1) {        // split: waves per task, each with a contiguous share of the task's sub-chunks (small problems: more waves per SIMD)
     const DetScal ds{scal, lacc};
-    constexpr int off = (DC == 6) ? 0 : 3;
     extern __shared__ __attribute__((aligned(16))) double sB[];          // per wave: k_gram_backsub's records | point records [2][8][GBS2_PT]: X at 0, PS at 4
     if (res_r && blockIdx.x == gridDim.x - 1) { __shared__ double red[4 * 4]; residual_check_body(Nc * DC, y, res_b, res_q, res_Sfc, res_Sff, res_tol2, res_r, res_pcg, red); return; }
     const int nwg = res_r ? (int)gridDim.x - 1 : (int)gridDim.x;
@@ -2047,11 +2113,24 @@ k_gram_backsub2(const double* __restrict__ cam, const double* __restrict__ rot, 
     const int camv = rec[4 + (lane & (GRAM_KMAX - 1))];                 // the task's cameras as a lane vector (gram_cam_of)
     gram_gather<33, GRAM_CAMREC, 6>(cam, rot, camv, K, lane, sCam);
     gram_gather<GBS_CAMC, GBS_CAMC, 3>(cam_c, rot_c, camv, K, lane, sCamC);
-    { const int k = min(lane / DC, K - 1), a = lane - DC * (lane / DC), c = gram_cam_of(camv, k); const double st = scale_cam[6 * c + off + a] * y[c * DC + a]; if (lane < DC * K) sStep[6 * k + a] = st; }
+    // per camera k of the task: sStep[6 k ..] = [scaled translation step (6-dof) | q = M (scaled rotation step)] -- what lin_obs_model needs; lane k < K forms both (camv of lane k is camera k)
+    if (lane < K) {
+        const int c = camv;
+        double dr[3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            dr[i] = scale_cam[6 * c + 3 + i] * y[c * DC + (DC - 3) + i];
+            if (DC == 6) sStep[6 * lane + i] = scale_cam[6 * c + i] * y[c * DC + i];
+        }
+        const double* Mm = rot + 27 * (size_t)c + 18;
+#pragma unroll
+        for (int i = 0; i < 3; i++) sStep[6 * lane + 3 + i] = Mm[3 * i] * dr[0] + Mm[3 * i + 1] * dr[1] + Mm[3 * i + 2] * dr[2];
+    }
     const double f = focal[0], sf = scale_f[0], yf = y[Nc * DC], fcand = focal_c[0];
     const int lq = lane & (GRAM_SUB - 1), lp = lane >> 3;               // observation (= camera of the group), point of the sub-chunk
     const int kq = min(lq, K - 1);
     double acc[4] = {0, 0, 0, 0};   // model, step2, xn2, candidate cost
+    CostAcc cost(la);               // (one factor per sub-chunk of this lane: the split decides which)
     // the wave's three record loads of a sub-chunk: A lanes [0, 24) X; B entries [0, 64) of the 8 x 12 doubles of PS, C entries [64, 96)
     const int a_i = lane / 3, a_k = lane - 3 * a_i, b_i = lane / 12, b_k = lane - 12 * b_i, c_i = (64 + lane) / 12, c_k = 64 + lane - 12 * c_i;
     const int a_dst = a_i * GBS2_PT + a_k, b_dst = b_i * GBS2_PT + 4 + b_k, c_dst = c_i * GBS2_PT + 4 + c_k;
@@ -2090,15 +2169,9 @@ k_gram_backsub2(const double* __restrict__ cam, const double* __restrict__ rot, 
         double m0 = 0.0, m1 = 0.0, r0 = 0.0, r1 = 0.0, J0[3] = {0, 0, 0}, J1[3] = {0, 0, 0}, w[3] = {0, 0, 0};
         if (act) {
             const double* crec = sCam + kq * GRAM_CAMREC;
-            ObsLin L; lin_obs<DC == 6>(f, crec, crec + 6, Xn, on.x, on.y, loss, la, L);
-            double Jc[2][DC]; cam_block_raw<DC>(L, Jc);
-            m0 = L.Jf[0] * sf * yf; m1 = L.Jf[1] * sf * yf; r0 = L.r[0]; r1 = L.r[1];
-#pragma unroll
-            for (int a = 0; a < DC; a++) {
-                const double ya = sStep[6 * kq + a];
-                if (!jc_zero<DC>(0, a)) m0 += Jc[0][a] * ya;
-                if (!jc_zero<DC>(1, a)) m1 += Jc[1][a] * ya;
-            }
+            const double* st = sStep + 6 * kq;
+            ObsModel L; lin_obs_model<DC == 6>(f, crec, crec + 6, Xn, on.x, on.y, loss, la, st, st + 3, L);
+            m0 = L.Jf[0] * sf * yf + L.mc[0]; m1 = L.Jf[1] * sf * yf + L.mc[1]; r0 = L.r[0]; r1 = L.r[1];
 #pragma unroll
             for (int k = 0; k < 3; k++) { J0[k] = L.Jp[0][k]; J1[k] = L.Jp[1][k]; w[k] = J0[k] * m0 + J1[k] * m1; }
         }
@@ -2110,9 +2183,9 @@ k_gram_backsub2(const double* __restrict__ cam, const double* __restrict__ rot, 
         if (act) {
             const double M0 = m0 + J0[0] * u[0] + J0[1] * u[1] + J0[2] * u[2], M1 = m1 + J1[0] * u[0] + J1[1] * u[1] + J1[2] * u[2];
             acc[0] += -(M0 * r0 + M1 * r1) + 0.5 * (M0 * M0 + M1 * M1);
-            const double* cc = sCamC + kq * GBS_CAMC;
-            acc[3] += obs_cost(fcand, cc, cc + 3, Xc, on.x, on.y, loss, la);
         }
+        cost_room(cost, loss, la, 1);
+        { const double* cc = sCamC + kq * GBS_CAMC; obs_cost_acc(fcand, cc, cc + 3, Xc, on.x, on.y, loss, la, cost, act); }
         if (valid && lq == 0) {                                          // the point's candidate and step norms, once per point (a fixed point: zero record, zero step, not counted)
 #pragma unroll
             for (int k = 0; k < 3; k++) pts_c[3 * pn + k] = Xc[k];
@@ -2122,6 +2195,7 @@ k_gram_backsub2(const double* __restrict__ cam, const double* __restrict__ rot, 
     }
 #undef GBS2_LOAD
 #undef GBS2_STAGE_STORE
+    cost_flush(cost, loss, la); acc[3] = cost.sum;
     const double t = wave_transpose_sum(acc);
     const int slot = wave_tr_index();
     double* sl = scal + (size_t)((blockIdx.x * (blockDim.x >> 6) + wave) & (SC_NSLOT - 1)) * SC_TOTAL;

@@ -292,7 +292,7 @@ struct LmRun {
             LAUNCH(h, KID_SCHUR_GRAM, (k_schur_gram_any<DC>), ng, 64, gram_lds, at.cam, at.rot, at.pts, at.focal, oxy, ng, h->gr_rec.p, h->scale_cam.p, h->scale_f.p, h->Vs.p, loss, la, rows_alloc,
                    F.focal_free ? 1 : 0, gram_t4() ? 1 : 0, z.S_val, z.rhs, z.Udiag, z.Sfc, z.gcraw, z.det);
         } else {
-            GramFuse fz; fz.scale_pt = h->scale_pt.p; fz.radius = radius; fz.min_diag = O.min_lm_diagonal; fz.max_diag = O.max_lm_diagonal; fz.PS_out = h->Vs.p; fz.gp_out = h->gp.p; fz.scal = z.scal; fz.emit_skip = SSFM_LAB_KNOB("SSFM_GRAM_EMIT_SKIP", 0); fz.spec = spec;
+            GramFuse fz; fz.scale_pt = h->scale_pt.p; fz.radius = radius; fz.min_diag = O.min_lm_diagonal; fz.max_diag = O.max_lm_diagonal; fz.PS_out = h->Vs.p; fz.LF_out = h->Lf.p; fz.gp_out = h->gp.p; fz.scal = z.scal; fz.emit_skip = SSFM_LAB_KNOB("SSFM_GRAM_EMIT_SKIP", 0); fz.spec = spec;
             for (int cl = 0; cl < (DC == 6 ? 5 : 3); cl++) {              // (3-dof cameras: two row tiles at most)
                 const int t0 = cl ? cls_end[cl - 1] : 0, t1 = cls_end[cl];
                 if (t1 <= t0) continue;
@@ -842,6 +842,7 @@ static int ba_create_impl(ssfm_ctx* ctx, const ssfm_ba_problem* p, const ssfm_ba
     AL(diag_cam, (size_t)Nc * 6); AL(diag_pt, (size_t)nP * 3); AL(diag_f, 1);
     AL(lmdev, 2);
     AL(Vs, (size_t)nP * 12); AL(gp, (size_t)nP * 3);
+    AL(Lf, (size_t)nP * 6);                        // Cholesky factor of the scaled V^-1 per point: written and read by the fused Gram task only (GramFuse::LF_out)
     const size_t nnzb = (size_t)F.row_ptr[Nc], n = (size_t)Nc * DC;
     const size_t n_red = nnzb * DC * DC + (n + 1) + 3 * n + SC_NSUM + (size_t)ctx->nranks;   // ... | scalar sums | gradient-max slot per rank
     h->n_red = (int)n_red;

@@ -152,6 +152,29 @@ SSFM_HD void robust_loss(int type, double a, double s, double& rho0, double& rho
     } else { rho0 = s; rho1 = 1.0; }
 }
 
+// ---- sum of logs as the log of a product:  sum_i log(x_i) = log(prod_i x_i) ---------------------------------
+// The Cauchy cost is b log(1 + s/b) per observation and only its SUM is ever used; an fp64 log is ~90 dependent vector instructions on the device.  A factor
+// x = m 2^e (frexp: m in [0.5, 1)) multiplies a running mantissa product and adds to an integer exponent sum: four instructions.  logprod_flush returns
+// log(product) and resets; the caller flushes at least once per LOGPROD_MAX factors, so that the mantissa product (>= 2^-64) cannot underflow.  The flush splits the
+// product once more and takes the log of a value in [1, 2): factors that are all exactly 1 give exactly 0, and a product of factors >= 1 is a sum of two
+// non-negative terms.  A factor of +inf or NaN makes the product, and so the flushed value, non-finite, as log(x) would have been.
+constexpr int LOGPROD_MAX = 64;
+struct LogProd { double m = 1.0; int e = 0; };
+SSFM_HD double frexp_split(double x, int& e) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    e = __builtin_amdgcn_frexp_exp(x); return __builtin_amdgcn_frexp_mant(x);
+#else
+    return frexp(x, &e);
+#endif
+}
+SSFM_HD void logprod_mul(LogProd& a, double x) { int e; a.m *= frexp_split(x, e); a.e += e; }
+SSFM_HD double logprod_flush(LogProd& a) {
+    int e; const double m = frexp_split(a.m, e);                              // product = m 2^(e + a.e) = (2 m) 2^(e + a.e - 1), 2 m in [1, 2)
+    const double r = log(2.0 * m) + (double)(e + a.e - 1) * 0.693147180559945309417232121458;
+    a.m = 1.0; a.e = 0;
+    return r;
+}
+
 // symmetric 3x3 (xx xy xz yy yz zz) inverse by cofactors
 SSFM_HD void sym3_inverse(const double* V, double* Vi) {
     const double c00 = V[3] * V[5] - V[4] * V[4], c01 = V[2] * V[4] - V[1] * V[5], c02 = V[1] * V[4] - V[2] * V[3];
