@@ -379,6 +379,47 @@ int ssfm_match_pairs(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr,
 int ssfm_match_knn_probe(ssfm_ctx* ctx, int32_t n0, const float* train, int32_t n1, const float* query, int32_t dim, int32_t* nn, float* dist);
 /* Device time of the kernels of this context's last ssfm_match_pairs call, summed over its slabs (like ssfm_ransac_last_kernel_ms). */
 int ssfm_match_last_kernel_ms(ssfm_ctx* ctx, double* ms);
+/* ---- guided matching: rematch a verified pair under its essential matrix (no reference counterpart; COLMAP's guided_matching) ----------------
+ * Lowe's test over the whole train frame drops a feature on repeated structure before geometry is consulted.  Once a pair has an E, the test is
+ * repeated among the train features inside the query's epipolar band only.  THE RULE, for pair p with train = frame pair_frame0[p] (n0 features,
+ * rays u_j), query = frame pair_frame1[p] (n1 features, rays v_i) and E_p (9 doubles, column-major) in the convention of ssfm_sampson_probe,
+ * v_i^T E u_j = 0 for a true correspondence:
+ *     b_j = E u_j      a_i = E^T v_i      d = v_i . b_j      den = b_j.x^2 + b_j.y^2 + a_i.x^2 + a_i.y^2
+ *     cand(i, j)  <=>  d * d < squared_threshold * den
+ * evaluated in fp64 without a division; a NaN, or 0 < 0, is "no", so a zero E or a zero threshold admits nothing.  This is
+ * SphericalEstimator::EvaluateModelOnPoint (src/spherical_estimator.cpp:67-78) below the threshold, in the unit of the squared_inlier_threshold of the
+ * RANSAC calls.  Per query i: AMONG ITS CANDIDATES ONLY, j1 and j2 are the nearest and second nearest train rows by the distance of ssfm_match_pairs (float
+ * sqrtf(sum (q - t)^2), the finalists re-evaluated in the direct form, equal distances rank the lower j first).  Query i is accepted iff j1 exists, and
+ * dist1 <= max_distance, and j2 does not exist or (double)dist1 < ratio * (double)dist2.  Then m01[j1] = i, the largest accepted i keeps a train slot: the
+ * list of a pair is (j, i) in ascending j, each j and each i at most once -- the match_idx0 / match_idx1 shape of ssfm_match_pairs.  The mask applies BEFORE
+ * the ranking ("plain match, then filter" is another, weaker rule); a lone candidate is accepted, so a train frame of one feature can match here.
+ * E of ssfm_ransac5_batch_indexed / ssfm_pairwise5_from_features has this convention as returned (the residual there is taken on v^T E u; checked on the
+ * call's own inliers in tests/test_guided_match_gpu.py), no transposition is needed; for the spherical front end, which returns R only, E = [t]x R with
+ * t = R e_z - e_z, negated when inward (make_spherical_essential_matrix, src/spherical_utils.cpp:9-14).
+ * Device: k_guided_dist, the tiling of the plain distance kernel with (E u_j, b.x^2 + b.y^2) of a staged train tile and (v_i, a.x^2 + a.y^2) of the query
+ * tile in LDS (8 KB more); the predicates of a tile are packed into a bit mask per query that the ranking epilogue tests.  Bit-identical from run to run. */
+typedef struct {
+    double ratio;              /* 0.75 */
+    double squared_threshold;  /* 0: the caller sets it (nothing is admitted at 0) */
+    float max_distance;        /* +inf */
+    int32_t dim;               /* 128; a multiple of 4, 4..128 */
+} ssfm_guided_match_options;   /* 24 bytes */
+void ssfm_guided_match_default_options(ssfm_guided_match_options* o);
+/* Feature tables, pair list, slabs (SSFM_MATCH_SLAB_PAIRS), capacity protocol (match_ptr always written, NULL lists = counts only, SSFM_ERR_INVALID with
+ * the needed total in match_ptr[num_pairs]) and argument checks before any launch: those of ssfm_match_pairs.  In addition feat_rays
+ * ([feat_ptr[num_frames] * 3], as ssfm_ransac_batch_indexed takes them) and E ([9 * num_pairs]) must not be NULL when num_pairs > 0, squared_threshold >= 0
+ * and not NaN, max_distance >= 0.  Single-GPU: a context with a communicator is refused.  Up: the descriptors, 24 bytes per feature, 72 per pair; down: the
+ * count scan and 8 bytes per match. */
+int ssfm_guided_match_pairs(ssfm_ctx* ctx, int32_t num_frames, const int32_t* feat_ptr, const float* descs, const double* feat_rays, int32_t num_pairs,
+                            const int32_t* pair_frame0, const int32_t* pair_frame1, const double* E, const ssfm_guided_match_options* o, int64_t capacity,
+                            int32_t* match_ptr, int32_t* match_idx0, int32_t* match_idx1);
+/* Parity probe of ONE pair (train rows with rays u, query rows with rays v): nn [n1 * 2] the two finalists among the candidates (-1 where absent),
+ * dist [n1 * 2] their float distances (+inf where absent), cand_count [n1] the number of train rows inside the band of query i -- the predicate is
+ * evaluated for all n0 x n1 entries here. */
+int ssfm_guided_knn_probe(ssfm_ctx* ctx, int32_t n0, const float* train, const double* u, int32_t n1, const float* query, const double* v, int32_t dim,
+                          const double* E, double squared_threshold, int32_t* nn, float* dist, int32_t* cand_count);
+/* Device time of the kernels of this context's last ssfm_guided_match_pairs call, summed over its slabs (like ssfm_match_last_kernel_ms). */
+int ssfm_guided_match_last_kernel_ms(ssfm_ctx* ctx, double* ms);
 
 /* ---- the pairwise front end in one call: match_exhaustive + estimate_pairwise (examples/spherical_sfm_tools.cpp:575-600, :309-420) -------------
  * For the given frame pairs, from the per-frame feature tables (descs: dim floats per feature; feat_rays: Kinv (x, y, 1), 3 doubles per feature; both

@@ -75,6 +75,10 @@ class MatchOptionsC(C.Structure):
     _fields_ = [("ratio", C.c_double), ("dim", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GuidedMatchOptionsC(C.Structure):
+    _fields_ = [("ratio", C.c_double), ("squared_threshold", C.c_double), ("max_distance", C.c_float), ("dim", C.c_int32)]
+
+
 class RotL1OptionsC(C.Structure):
     _fields_ = [("max_iterations", C.c_int32), ("step_tolerance", C.c_double), ("weight_floor", C.c_double), ("pcg_tolerance", C.c_double),
                 ("pcg_max_iterations", C.c_int32)]
@@ -110,6 +114,7 @@ DECLARED_SYMBOLS = [
     "ssfm_estimator_create", "ssfm_estimator_destroy", "ssfm_estimator_minimal_solver", "ssfm_estimator_non_minimal_solver",
     "ssfm_estimator_evaluate_model", "ssfm_estimator_least_squares", "ssfm_estimator_decompose",
     "ssfm_match_default_options", "ssfm_match_pairs", "ssfm_match_knn_probe", "ssfm_match_last_kernel_ms",
+    "ssfm_guided_match_default_options", "ssfm_guided_match_pairs", "ssfm_guided_knn_probe", "ssfm_guided_match_last_kernel_ms",
     "ssfm_pairwise_from_features", "ssfm_pairwise5_from_features", "ssfm_pairwise_front_last_kernel_ms",
     "ssfm_triplet_filter", "ssfm_view_graph_tree", "ssfm_focal_search_graph",
     "ssfm_rot_l1_default_options", "ssfm_rot_l1_init",
@@ -225,6 +230,13 @@ def lib():
     L.ssfm_match_pairs.restype = C.c_int
     L.ssfm_match_knn_probe.argtypes = [vp, C.c_int32, c_float_p, C.c_int32, c_float_p, C.c_int32, c_i32_p, c_float_p]; L.ssfm_match_knn_probe.restype = C.c_int
     L.ssfm_match_last_kernel_ms.argtypes = [vp, c_double_p]; L.ssfm_match_last_kernel_ms.restype = C.c_int
+    L.ssfm_guided_match_default_options.argtypes = [C.POINTER(GuidedMatchOptionsC)]; L.ssfm_guided_match_default_options.restype = None
+    L.ssfm_guided_match_pairs.argtypes = [vp, C.c_int32, c_i32_p, c_float_p, c_double_p, C.c_int32, c_i32_p, c_i32_p, c_double_p, C.POINTER(GuidedMatchOptionsC), C.c_int64,
+                                          c_i32_p, c_i32_p, c_i32_p]
+    L.ssfm_guided_match_pairs.restype = C.c_int
+    L.ssfm_guided_knn_probe.argtypes = [vp, C.c_int32, c_float_p, c_double_p, C.c_int32, c_float_p, c_double_p, C.c_int32, c_double_p, C.c_double, c_i32_p, c_float_p, c_i32_p]
+    L.ssfm_guided_knn_probe.restype = C.c_int
+    L.ssfm_guided_match_last_kernel_ms.argtypes = [vp, c_double_p]; L.ssfm_guided_match_last_kernel_ms.restype = C.c_int
     L.ssfm_pairwise_from_features.argtypes = [vp, C.c_int32, c_i32_p, c_float_p, c_double_p, C.c_int32, c_i32_p, c_i32_p, C.POINTER(MatchOptionsC), C.POINTER(RansacOptionsC),
                                               C.c_double, C.c_int64, C.c_int64, c_i64_p, c_i32_p, c_double_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_u32_p]
     L.ssfm_pairwise_from_features.restype = C.c_int

@@ -12,7 +12,9 @@
 // -rotinit l1 (with -viewgraph; default: tree): the start is the robust one of ssfm_rot_l1_init instead of the tree chain, the matches whose residual at that start
 // exceeds -rotinitthresh degrees (default 2) are dropped, find_largest_connected_component runs once more, and refine_rotations starts from the L1 rotations of the
 // cameras that are left; rotinit.txt lists every pair with its residual.  One wrong match on a tree edge no longer rotates a whole subtree, and the gross outliers no longer bias the averaging.
-//   run_spherical_sfm -intrinsics <file: focal cx cy> -output <dir with the feature tracks> [-match | -pairwise] [-inward] [-width W -height H]
+// -guided (with -match): the accepted pairs are rematched under their own E(R) (guided_match -> ssfm_guided_match_pairs) before find_largest_connected_component:
+// features on repeated structure, which Lowe's test over the whole frame drops, come back.  GUIDED_RESULT reports the counts.  Without it nothing changes.
+//   run_spherical_sfm -intrinsics <file: focal cx cy> -output <dir with the feature tracks> [-match [-guided] | -pairwise] [-inward] [-width W -height H]
 //                     [-viewgraph [-tripletorder reference|composed] [-rotinit tree|l1] [-rotinitthresh DEG]] [-devicetracks]
 // -devicetracks: build_sfm's track pass runs on the device (ssfm_build_tracks_device: connected components, canonical point ids).  Without it nothing changes.
 #include <cmath>
@@ -25,7 +27,7 @@ using namespace sphericalsfm;
 
 int main(int argc, char** argv) {
     std::string intrinsics_path, output; bool inward = false, pairwise = false, match_mode = false, viewgraph = false; int triplet_order = SSFM_TRIPLET_ORDER_REFERENCE, width = 1920, height = 1080, mininliers = 100; double inlierthresh = 2.0;
-    bool rotinit_l1 = false, device_tracks = false; double rotinit_thresh_deg = 2.0;
+    bool rotinit_l1 = false, device_tracks = false, guided = false; double rotinit_thresh_deg = 2.0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "-intrinsics" && i + 1 < argc) intrinsics_path = argv[++i];
@@ -36,6 +38,7 @@ int main(int argc, char** argv) {
         else if (a == "-devicetracks") device_tracks = true;                // build_sfm's track pass on the device (ssfm_build_tracks_device); default: the host pass
         else if (a == "-pairwise") pairwise = true;                         // matches.dat holds raw matches: run estimate_pairwise (GPU RANSAC) first
         else if (a == "-match") match_mode = true;                          // no matches.dat: features -> verified image matches on the device
+        else if (a == "-guided") guided = true;                             // with -match: rematch the accepted pairs under their E
         else if (a == "-inlierthresh" && i + 1 < argc) inlierthresh = std::atof(argv[++i]);
         else if (a == "-mininliers" && i + 1 < argc) mininliers = std::atoi(argv[++i]);
         else if (a == "-sequential") viewgraph = false;                     // the default: rotations chained over the matches (k-1, k)
@@ -54,6 +57,7 @@ int main(int argc, char** argv) {
         else { std::cout << "unknown argument " << a << "\n"; return 2; }
     }
     if (rotinit_l1 && !viewgraph) { std::cout << "-rotinit l1 needs -viewgraph\n"; return 2; }
+    if (guided && !match_mode) { std::cout << "error: -guided needs -match\n"; return 1; }
     if (intrinsics_path.empty() || output.empty()) { std::cout << "usage: run_spherical_sfm -intrinsics <file> -output <dir> [-inward]\n"; return 2; }
     double focal, centerx, centery;
     std::ifstream intrinsicsf(intrinsics_path);
@@ -75,6 +79,13 @@ int main(int argc, char** argv) {
         const size_t nframes = keyframes.size();
         loop_closures = estimate_pairwise_from_features(sfm.GetContext(), intrinsics, keyframes, inlierthresh, mininliers, inward, image_matches);
         if (loop_closures == 0) { std::cout << "error: no loop closures found\n"; return 1; }
+        if (guided) {
+            size_t before = 0, after = 0;
+            for (const ImageMatch& im : image_matches) before += im.matches.size();
+            guided_match(sfm.GetContext(), intrinsics, keyframes, image_matches, inlierthresh, inward);
+            for (const ImageMatch& im : image_matches) after += im.matches.size();
+            std::printf("GUIDED_RESULT pairs=%zu matches_before=%zu matches_after=%zu\n", image_matches.size(), before, after);
+        }
         find_largest_connected_component(keyframes, image_matches);
         std::cout << "kept " << keyframes.size() << " of " << nframes << " keyframes, " << image_matches.size() << " image pairs, " << loop_closures << " loop closures\n";
     } else if (pairwise) {                                                          // run_spherical_sfm.cpp:56-63

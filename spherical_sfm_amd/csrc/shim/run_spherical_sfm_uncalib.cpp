@@ -14,8 +14,10 @@
 // -fivepoint: the pairwise stage is general relative pose (estimate_pairwise_five_point, examples/run_spherical_sfm_uncalib.cpp:107-110) instead of the spherical
 // three-point estimator: with -match in one device call from the feature tables (estimate_pairwise_five_point_from_features: the match lists stay on the
 // device), without it on the matches of matches.dat, whose rotations it replaces.
+// -guided (with -match): the accepted pairs are rematched under their own essential matrix at the guessed focal -- E(R) of the spherical estimator, the E of
+// the five-point estimator with -fivepoint -- before find_largest_connected_component (guided_match -> ssfm_guided_match_pairs).  GUIDED_RESULT reports the counts.
 //   run_spherical_sfm_uncalib -output <dir with keyframes.txt, features.dat, matches.dat> -width W -height H [-generalba] [-inward]
-//                             [-match] [-fivepoint] [-inlierthresh T] [-mininliers N] [-viewgraph [-rotinit tree|l1] [-rotinitthresh DEG]] [-devicetracks]
+//                             [-match [-guided]] [-fivepoint] [-inlierthresh T] [-mininliers N] [-viewgraph [-rotinit tree|l1] [-rotinitthresh DEG]] [-devicetracks]
 // -devicetracks: build_sfm's track pass runs on the device (ssfm_build_tracks_device: connected components, canonical point ids).  Without it nothing changes.
 #include <cmath>
 #include <cstdio>
@@ -26,7 +28,7 @@ using namespace sphericalsfm;
 
 int main(int argc, char** argv) {
     std::string output; bool inward = false, generalba = false, match_mode = false, viewgraph = false, fivepoint = false; int width = 0, height = 0, num_trials = 1024, mininliers = 100; unsigned seed = 0; double inlierthresh = 2.0;
-    bool rotinit_l1 = false, device_tracks = false; double rotinit_thresh_deg = 2.0;
+    bool rotinit_l1 = false, device_tracks = false, guided = false; double rotinit_thresh_deg = 2.0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "-output" && i + 1 < argc) output = argv[++i];
@@ -39,6 +41,7 @@ int main(int argc, char** argv) {
         else if (a == "-generalba") generalba = true;
         else if (a == "-match") match_mode = true;
         else if (a == "-fivepoint") fivepoint = true;
+        else if (a == "-guided") guided = true;                             // with -match: rematch the accepted pairs under their E
         else if (a == "-inlierthresh" && i + 1 < argc) inlierthresh = std::atof(argv[++i]);
         else if (a == "-mininliers" && i + 1 < argc) mininliers = std::atoi(argv[++i]);
         else if (a == "-sequential") viewgraph = false;
@@ -53,6 +56,7 @@ int main(int argc, char** argv) {
     }
     if (output.empty() || width <= 0 || height <= 0) { std::cout << "usage: run_spherical_sfm_uncalib -output <dir> -width W -height H [-generalba] [-inward]\n"; return 2; }
     if (rotinit_l1 && !viewgraph) { std::cout << "-rotinit l1 needs -viewgraph\n"; return 2; }
+    if (guided && !match_mode) { std::cout << "error: -guided needs -match\n"; return 1; }
     std::vector<Keyframe> keyframes; std::vector<ImageMatch> image_matches;
     const double focal_guess = (width + height) / 2, centerx = width / 2, centery = height / 2;     // :101-103 (integer division as in the reference)
     if (match_mode ? !read_features(output, keyframes) : (!read_feature_tracks(output, keyframes, image_matches) || image_matches.empty())) { std::cout << "error: no matches found\n"; return 1; }
@@ -61,18 +65,30 @@ int main(int argc, char** argv) {
 
     SfM sfm_probe(Intrinsics(focal_guess, centerx, centery));                                       // owns the library context for the pairwise stage and the search
     int loop_closures = -1;
+    std::vector<Mat3> guided_Es;                                                                    // -fivepoint -guided: the E of every accepted pair
+    auto rematch = [&]() {                                                                          // -guided: before the component step renumbers the frames
+        size_t before = 0, after = 0;
+        for (const ImageMatch& im : image_matches) before += im.matches.size();
+        if (fivepoint) guided_match(sfm_probe.GetContext(), Intrinsics(focal_guess, centerx, centery), keyframes, image_matches, guided_Es, inlierthresh);
+        else guided_match(sfm_probe.GetContext(), Intrinsics(focal_guess, centerx, centery), keyframes, image_matches, inlierthresh, inward);
+        for (const ImageMatch& im : image_matches) after += im.matches.size();
+        std::printf("GUIDED_RESULT pairs=%zu matches_before=%zu matches_after=%zu\n", image_matches.size(), before, after);
+    };
     if (fivepoint) {                                                                                // :107-110
-        if (match_mode) loop_closures = estimate_pairwise_five_point_from_features(sfm_probe.GetContext(), Intrinsics(focal_guess, centerx, centery), keyframes, inlierthresh, mininliers, image_matches);
+        if (match_mode) loop_closures = estimate_pairwise_five_point_from_features(sfm_probe.GetContext(), Intrinsics(focal_guess, centerx, centery), keyframes, inlierthresh, mininliers, image_matches,
+                                                                                   guided ? &guided_Es : nullptr);
         else {
             std::vector<ImageMatch> all; all.swap(image_matches);
             loop_closures = estimate_pairwise_five_point(sfm_probe.GetContext(), Intrinsics(focal_guess, centerx, centery), keyframes, all, inlierthresh, mininliers, image_matches);
         }
         if (loop_closures == 0) { std::cout << "error: no loop closures found\n"; return 1; }
+        if (guided) rematch();
         find_largest_connected_component(keyframes, image_matches);
         if (image_matches.empty()) { std::cout << "error: no matches found\n"; return 1; }
     } else if (match_mode) {                                                                        // :96-122
         loop_closures = estimate_pairwise_from_features(sfm_probe.GetContext(), Intrinsics(focal_guess, centerx, centery), keyframes, inlierthresh, mininliers, inward, image_matches);
         if (loop_closures == 0) { std::cout << "error: no loop closures found\n"; return 1; }
+        if (guided) rematch();
         find_largest_connected_component(keyframes, image_matches);
         if (image_matches.empty()) { std::cout << "error: no matches found\n"; return 1; }
     }

@@ -225,7 +225,7 @@ void match_exhaustive(ssfm_ctx* ctx, const std::vector<Keyframe>& keyframes, std
 
 // the two one-call front ends: exhaustive pairs, capacity bounds that cannot miss, the loop-closure count (five: ssfm_pairwise5_from_features, no `inward`)
 static int pairwise_front(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, double inlier_threshold, int min_num_inliers,
-                          bool five, bool inward, std::vector<ImageMatch>& image_matches_out) {
+                          bool five, bool inward, std::vector<ImageMatch>& image_matches_out, std::vector<Mat3>* Es_out = nullptr) {
     if (keyframes.size() < 2) return 0;
     const double kinv = 1.0 / intrinsics.focal;
     const double sq_thresh = inlier_threshold * inlier_threshold * kinv * kinv;           // :315, :440
@@ -239,13 +239,14 @@ static int pairwise_front(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std
     const int P = (int)pf0.size();
     int64_t pair_cap = P, inl_cap = 0, needed[2] = {0, 0};
     for (int p = 0; p < P; p++) inl_cap += std::min(feat_ptr[pf0[p] + 1] - feat_ptr[pf0[p]], feat_ptr[pf1[p] + 1] - feat_ptr[pf1[p]]);   // a pair has at most min(n0, n1) matches: never a miss
-    std::vector<int32_t> acc, nin, ptr, i0, i1; std::vector<double> R, t;
+    std::vector<int32_t> acc, nin, ptr, i0, i1; std::vector<double> R, t, E;
     for (int attempt = 0; attempt < 2; attempt++) {                                       // the capacity protocol (the bounds above cannot miss; a retry would repeat all the work)
         acc.assign((size_t)std::max<int64_t>(pair_cap, 1), 0); nin.assign(acc.size(), 0); ptr.assign((size_t)pair_cap + 1, 0); R.assign(9 * acc.size(), 0.0);
         i0.assign((size_t)std::max<int64_t>(inl_cap, 1), 0); i1.assign(i0.size(), 0);
-        if (five) t.assign(3 * acc.size(), 0.0);                                          // (ImageMatch has no place for t; E is not asked for)
+        if (five) t.assign(3 * acc.size(), 0.0);                                          // (ImageMatch has no place for t; E only for a caller that goes on to guided_match)
+        if (five && Es_out) E.assign(9 * acc.size(), 0.0);
         const int rc = five ? ssfm_pairwise5_from_features(ctx, (int32_t)fs.size(), feat_ptr.data(), descs.data(), rays.data(), P, pf0.data(), pf1.data(), nullptr, &O, sq_thresh,
-                                                           pair_cap, inl_cap, needed, acc.data(), R.data(), t.data(), nullptr, nin.data(), ptr.data(), i0.data(), i1.data(),
+                                                           pair_cap, inl_cap, needed, acc.data(), R.data(), t.data(), Es_out ? E.data() : nullptr, nin.data(), ptr.data(), i0.data(), i1.data(),
                                                            nullptr, nullptr, nullptr)
                             : ssfm_pairwise_from_features(ctx, (int32_t)fs.size(), feat_ptr.data(), descs.data(), rays.data(), P, pf0.data(), pf1.data(), nullptr, &O, sq_thresh,
                                                           pair_cap, inl_cap, needed, acc.data(), R.data(), nin.data(), ptr.data(), i0.data(), i1.data(), nullptr, nullptr, nullptr);
@@ -260,6 +261,7 @@ static int pairwise_front(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std
         Mat3 Rk; for (int q = 0; q < 9; q++) Rk[q] = R[9 * (size_t)a + q];
         if (index0 + 1 != index1) loop_closure_count++;
         image_matches_out.push_back(ImageMatch(index0, index1, inl, Rk));
+        if (five && Es_out) { Mat3 Ek; for (int q = 0; q < 9; q++) Ek[q] = E[9 * (size_t)a + q]; Es_out->push_back(Ek); }
     }
     return loop_closure_count;
 }
@@ -270,8 +272,54 @@ int estimate_pairwise_from_features(ssfm_ctx* ctx, const Intrinsics& intrinsics,
 }
 
 int estimate_pairwise_five_point_from_features(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, double inlier_threshold,
-                                               int min_num_inliers, std::vector<ImageMatch>& image_matches_out) {
-    return pairwise_front(ctx, intrinsics, keyframes, inlier_threshold, min_num_inliers, true, false, image_matches_out);
+                                               int min_num_inliers, std::vector<ImageMatch>& image_matches_out, std::vector<Mat3>* Es_out) {
+    return pairwise_front(ctx, intrinsics, keyframes, inlier_threshold, min_num_inliers, true, false, image_matches_out, Es_out);
+}
+
+void guided_match(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, std::vector<ImageMatch>& image_matches, const std::vector<Mat3>& Es,
+                  double inlier_threshold, double ratio, float max_distance) {
+    if (Es.size() != image_matches.size()) { std::cout << "error: guided_match: one E per image match\n"; std::exit(1); }
+    if (image_matches.empty()) return;
+    const double kinv = 1.0 / intrinsics.focal;
+    std::vector<const Features*> fs; for (const Keyframe& k : keyframes) fs.push_back(&k.features);
+    std::vector<int32_t> feat_ptr, pf0, pf1; std::vector<float> descs; std::vector<double> rays, E;
+    feature_tables(fs, &intrinsics, feat_ptr, descs, &rays);
+    int64_t cap = 0;
+    for (size_t p = 0; p < image_matches.size(); p++) {
+        const int a = image_matches[p].index0, b = image_matches[p].index1;
+        if (a < 0 || b < 0 || a >= (int)fs.size() || b >= (int)fs.size()) { std::cout << "error: guided_match: an image match names a keyframe that is not there\n"; std::exit(1); }
+        pf0.push_back(a); pf1.push_back(b); E.insert(E.end(), Es[p].begin(), Es[p].end());
+        cap += std::min(feat_ptr[a + 1] - feat_ptr[a], feat_ptr[b + 1] - feat_ptr[b]);      // a pair has at most min(n0, n1) matches
+    }
+    ssfm_guided_match_options O; ssfm_guided_match_default_options(&O);
+    O.ratio = ratio; O.max_distance = max_distance; O.squared_threshold = inlier_threshold * inlier_threshold * kinv * kinv;     // the unit of estimate_pairwise (:315)
+    const int P = (int)pf0.size();
+    std::vector<int32_t> mp((size_t)P + 1, 0), m0((size_t)std::max<int64_t>(cap, 1), 0), m1((size_t)std::max<int64_t>(cap, 1), 0);
+    if (ssfm_guided_match_pairs(ctx, (int32_t)fs.size(), feat_ptr.data(), descs.data(), rays.data(), P, pf0.data(), pf1.data(), E.data(), &O, cap, mp.data(), m0.data(),
+                                m1.data()) != SSFM_OK) {
+        std::cout << "error: " << ssfm_last_error(ctx) << "\n"; std::exit(1);
+    }
+    for (int p = 0; p < P; p++) {
+        Matches m; for (int32_t k = mp[p]; k < mp[p + 1]; k++) m[(size_t)m0[k]] = (size_t)m1[k];
+        image_matches[(size_t)p].matches.swap(m);
+    }
+}
+
+void guided_match(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, std::vector<ImageMatch>& image_matches, double inlier_threshold,
+                  bool inward, double ratio, float max_distance) {
+    std::vector<Mat3> Es;
+    for (const ImageMatch& im : image_matches) {                                          // make_spherical_essential_matrix (src/spherical_utils.cpp:9-14); Mat3 is column-major
+        const Mat3& R = im.R;
+        double t[3] = {R[6], R[7], R[8] - 1.0};                                           // R e_z - e_z
+        if (inward) { t[0] = -t[0]; t[1] = -t[1]; t[2] = -t[2]; }
+        Mat3 E;
+        for (int c = 0; c < 3; c++) {                                                     // column c of [t]x R = t x (column c of R)
+            const double* r = &R[3 * c];
+            E[3 * c] = t[1] * r[2] - t[2] * r[1]; E[3 * c + 1] = t[2] * r[0] - t[0] * r[2]; E[3 * c + 2] = t[0] * r[1] - t[1] * r[0];
+        }
+        Es.push_back(E);
+    }
+    guided_match(ctx, intrinsics, keyframes, image_matches, Es, inlier_threshold, ratio, max_distance);
 }
 
 void initialize_rotations_sequential(int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations) {

@@ -4,6 +4,7 @@
 #pragma once
 #include <array>
 #include <cstddef>
+#include <limits>
 #include <map>
 #include <string>
 #include <vector>
@@ -100,8 +101,19 @@ int estimate_pairwise_from_features(ssfm_ctx* ctx, const Intrinsics& intrinsics,
 // match_exhaustive + estimate_pairwise_five_point in one device call (ssfm_pairwise5_from_features), built like estimate_pairwise_from_features: all pairs
 // index0 < index1, capacity bounds that cannot miss, the loop-closure count.  Same result and return value as match_exhaustive followed by
 // estimate_pairwise_five_point.  Single-GPU: the context must not carry a communicator.
+// Es_out (optional): the essential matrix of every appended ImageMatch, column-major, v^T E u = 0 with u in index0 -- what guided_match takes.
 int estimate_pairwise_five_point_from_features(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, double inlier_threshold,
-                                               int min_num_inliers, std::vector<ImageMatch>& image_matches_out);
+                                               int min_num_inliers, std::vector<ImageMatch>& image_matches_out, std::vector<Mat3>* Es_out = nullptr);
+
+// Guided matching (ssfm_guided_match_pairs; no reference counterpart): `matches` of every ImageMatch is replaced by its guided list -- Lowe's test among the
+// features of keyframes[index0] inside the epipolar band of each feature of keyframes[index1] -- under E = [t]x R, t = R e_z - e_z, negated if inward
+// (make_spherical_essential_matrix of the match's R).  The threshold is inlier_threshold^2 * Kinv(0)^2, as in estimate_pairwise.  index0 / index1 are positions in
+// `keyframes` (call it before find_largest_connected_component renumbers them); R stays.  One device call for all matches.  Single GPU.
+// The overload takes one E per ImageMatch instead (column-major, v^T E u = 0): the five-point path, where R alone does not give E.
+void guided_match(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, std::vector<ImageMatch>& image_matches, double inlier_threshold,
+                  bool inward, double ratio = 0.75, float max_distance = std::numeric_limits<float>::infinity());
+void guided_match(ssfm_ctx* ctx, const Intrinsics& intrinsics, const std::vector<Keyframe>& keyframes, std::vector<ImageMatch>& image_matches, const std::vector<Mat3>& Es,
+                  double inlier_threshold, double ratio = 0.75, float max_distance = std::numeric_limits<float>::infinity());
 
 void initialize_rotations_sequential(int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations);   // tools.cpp:794-813
 double refine_rotations(ssfm_ctx* ctx, int num_cameras, const std::vector<ImageMatch>& image_matches, std::vector<Mat3>& rotations); // tools.cpp:851-860

@@ -28,6 +28,7 @@ struct ssfm_ctx {
     double* host_pub = nullptr; unsigned long long pub_seq = 0;
     double ransac_kernel_ms = 0.0;      // device time of the kernels of the last ssfm_ransac_batch* call (hipEvent brackets per slab), ssfm_ransac_last_kernel_ms
     double match_kernel_ms = 0.0;       // the same for the last ssfm_match_pairs call, ssfm_match_last_kernel_ms
+    double guided_kernel_ms = 0.0;      // the same for the last ssfm_guided_match_pairs call, ssfm_guided_match_last_kernel_ms
     double front_kernel_ms = 0.0;       // the same for the last ssfm_pairwise_from_features / ssfm_pairwise5_from_features call (its matching + its RANSAC slabs, hand-over kernels included)
     double anms_kernel_ms = 0.0;        // the same for the last ssfm_anms_batch call (one event pair round its launches), ssfm_anms_last_kernel_ms
     double tracks_kernel_ms = 0.0;      // the same for the last ssfm_build_tracks_device call, ssfm_tracks_last_kernel_ms

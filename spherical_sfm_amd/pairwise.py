@@ -90,6 +90,35 @@ def pairwise5_from_features(ctx, descs, rays, feat_ptr, pairs, match_options=Non
     return _front(True, ctx, descs, rays, feat_ptr, pairs, match_options, ransac_options, sq_thresh, pair_capacity, inlier_capacity, want_E)
 
 
+def spherical_essential(R, inward=False):
+    """make_spherical_essential_matrix (src/spherical_utils.cpp:9-14): E = [t]x R with t = R e_z - e_z, negated if inward -- the arithmetic of the device's
+    make_E_dev.  R (3, 3) or (A, 3, 3) -> E of the same shape, v^T E u = 0 for u in frame0 and v in frame1."""
+    R = np.asarray(R, np.float64)
+    Rs = R.reshape(-1, 3, 3)
+    E = np.zeros_like(Rs)
+    for a, Ra in enumerate(Rs):
+        t = np.array([Ra[0, 2], Ra[1, 2], Ra[2, 2] - 1.0])
+        if inward:
+            t = -t
+        E[a, 0] = t[1] * Ra[2] - t[2] * Ra[1]; E[a, 1] = t[2] * Ra[0] - t[0] * Ra[2]; E[a, 2] = t[0] * Ra[1] - t[1] * Ra[0]
+    return E.reshape(R.shape)
+
+
+def guided_rematch(ctx, descs, rays, feat_ptr, pairs, result, sq_thresh, inward=False, ratio=0.75, max_distance=np.inf):
+    """Guided matching (match.guided_match_flat) of the ACCEPTED pairs of a PairwiseResult under their own essential matrices: result.E where the
+    result carries one (pairwise5_from_features with want_E), otherwise spherical_essential(result.R, inward).  -> a PairwiseResult with the same
+    accepted pairs, poses and per-pair statistics whose inlier lists (inl_ptr, inl_idx0, inl_idx1, num_inliers) are the guided lists."""
+    pr = np.asarray(pairs, np.int32).reshape(-1, 2)[result.accepted_pair]
+    E = result.E if getattr(result, "E", None) is not None else spherical_essential(result.R, inward)
+    mp, m0, m1 = _match.guided_match_flat(ctx, feat_ptr, descs, rays, pr[:, 0], pr[:, 1], np.asarray(E).reshape(-1, 3, 3), sq_thresh, ratio=ratio, max_distance=max_distance)
+    out = PairwiseResult()
+    for k in PairwiseResult.__slots__:
+        if hasattr(result, k):
+            setattr(out, k, getattr(result, k))
+    out.inl_ptr = mp; out.inl_idx0 = m0; out.inl_idx1 = m1; out.num_inliers = np.diff(mp).astype(np.int32)
+    return out
+
+
 def last_kernel_ms(ctx):
     """device time of the kernels of the context's last pairwise_from_features / pairwise5_from_features call (ssfm_pairwise_front_last_kernel_ms)"""
     ms = C.c_double(0)
