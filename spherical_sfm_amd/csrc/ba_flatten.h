@@ -937,9 +937,11 @@ inline void ba_flatten(const ssfm_ba_problem& P, int nranks, int rank, BAFlat& F
             int gram_pts = gram_pts_env;
             if (gram_pts <= 0) {
                 gram_pts = (int)std::min<int64_t>(192, std::max<int64_t>(64, (F.gram_points / 4608 + 15) / 16 * 16));
-                // round 4: a small problem runs fastest with ONE wave per SIMD -- the shortest task length (64..192) that leaves at most 4 x CUs tasks, runs cut in equal
-                // parts.  Config 2 (300 runs of 333 points): 3 x 112 = 900 tasks 43.9 us; 6 x 56 = 1800 tasks (two waves on three of four SIMDs) 48.2; the
-                // 5 x 64 + 13 of round 3 46.1; 2 x 168 = 600 tasks 49.6 (scripts/prof_gram_ld.py with SSFM_GRAM_PTS, profiles/r04_notes.md)
+                // round 4: a small problem runs fastest with at most ONE TASK per SIMD -- the shortest task length (64..192) that leaves at most 4 x CUs tasks, runs cut
+                // in equal parts.  Config 2 (300 runs of 333 points): 3 x 112 = 900 tasks 43.9 us; 6 x 56 = 1800 tasks (two waves on three of four SIMDs) 48.2; the
+                // 5 x 64 + 13 of round 3 46.1; 2 x 168 = 600 tasks 49.6 (scripts/prof_gram_ld.py with SSFM_GRAM_PTS, profiles/r04_notes.md).  Round 11: not one WAVE --
+                // two waves that SHARE a task (head and emission paid once: ba_kernels.h k_schur_gram_split, ba_solver.hip LmRun::gram_split) beat the single one,
+                // 46.5 -> 42.5 us at 3 x 112; the cut itself stays: 2 x 168 with two / three waves per task 51.8 / 58.6 us (profiles/r11_notes.md)
                 for (int g = 64; g <= 192; g += 8) {
                     int64_t tasks = 0; for (size_t r = 0; r < runs.size(); r += 2) tasks += (runs[r + 1] - runs[r] + g - 1) / g;
                     if (tasks <= 4 * (int64_t)num_cus) { gram_pts = g; break; }

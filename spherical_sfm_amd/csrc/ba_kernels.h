@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include "ssfm_math.h"
 #include "det_acc.h"
+#include "gram_share.h"
 
 namespace ssfm {
 
@@ -728,6 +729,8 @@ k_schur_pairs2(const double* __restrict__ cam, const double* __restrict__ rot, c
 #define SSFM_GRAM_LD 28      // row stride of the half products in LDS, doubles (swept in round 4: scripts/gpu_gram_ld.sh, profiles/r04_notes.md)
 #endif
 constexpr int GRAM_CAMREC = 34, GRAM_LD = SSFM_GRAM_LD, GRAM_SUB = GRAM_SUB_PTS, GRAM_TAIL = GRAM_KMAX * GRAM_CAMREC + 48 + GRAM_NPAIR / 2 + GRAM_KMAX / 2;
+constexpr int GRAM_VEC = 4 * 6 * GRAM_KMAX;      // split task: behind a wave's slice, its cameras' vectors [K][diag U | Jc^T r | coupling term | S_fc][DC]
+static_assert(GRAM_SUB == GRAM_SHARE_SUB, "gram_share.h deals sub-chunks of GRAM_SUB points");
 // transposing reduction over the 8 lanes that differ in lane bits 0..2: N values per lane in, ceil(N / 8) out; out[j] of a lane is the 8-lane sum of
 // value 8 j + 4 (lane & 1) + 2 ((lane >> 1) & 1) + ((lane >> 2) & 1)
 template <int N, int MASK>
@@ -750,7 +753,8 @@ struct OctTR<N, 0> { static __device__ __forceinline__ void run(double (&v)[N], 
 #pragma unroll
     for (int j = 0; j < N; j++) out[j] = v[j]; } };
 // W waves per workgroup, one task and one LDS slice each; the waves never talk to each other, so the two hand-overs per sub-chunk are wave-local
-// (LDS operations of one wave complete in order; the fences keep the compiler from moving them) instead of workgroup barriers.
+// (LDS operations of one wave complete in order; the fences keep the compiler from moving them) instead of workgroup barriers.  (The waves of a SPLIT task
+// meet once, at the barrier in front of the emission.)
 __device__ __forceinline__ void wave_lds_handover() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
@@ -805,7 +809,12 @@ __device__ __forceinline__ void chol3_scaled(const double* V, double* L) {
 // LF_out: 6 doubles per point, chol3_scaled of the record's V^-1 -- the prologue factors once per point what the unfused loop factors on every observation lane of every sub-chunk
 struct GramFuse { const double* scale_pt; double radius, min_diag, max_diag; double* PS_out; double* gp_out; double* scal; const double* spec; int emit_skip = 0; double* LF_out = nullptr; };
 // one wave task of k_schur_gram / k_schur_gram_any (below): the task's tile shape (NT, TI) is a template parameter, the task index an argument
-template <int DC, int NT, int TI, bool FUSE>
+// SPLIT (round 11): the W = blockDim.x / 64 waves of the workgroup SHARE the task -- wave w walks the sub-chunks [s_begin, s_end) of gram_share.h through the
+// prologue and the loop in its own LDS slice, talking to nobody; head (per wave, overlapped) and emission are paid once per task: every wave leaves its tiles, its
+// Jc^T Jc and its cameras' vectors in its slice, ONE workgroup barrier, then the blocks (dealt round-robin over the waves) and the vectors leave as the sum of the
+// W slices in slice order -- as many atomics per task as one wave issues (fewer: Jc^T r goes to rhs together with the coupling term).  A small problem (config 2:
+// 900 tasks on 1024 SIMDs, two waves of <= 256 registers each) then has two waves per SIMD covering each other's latencies.  !SPLIT is the kernel as it was.
+template <int DC, int NT, int TI, bool FUSE, bool SPLIT = false>
 __device__ __forceinline__ void
 schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, const double* __restrict__ pts, const double* __restrict__ focal,
                 const double2* __restrict__ obs_xy, const int* __restrict__ gr_rec, const double* __restrict__ scale_cam, const double* __restrict__ scale_f,
@@ -819,7 +828,8 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
     const long long t_0 = dbg ? wall_clock64() : 0;
     extern __shared__ __attribute__((aligned(16))) double sY[];          // per wave: [rows_alloc][GRAM_LD] | camera records [GRAM_KMAX][GRAM_CAMREC] | scales | slots | diagonal slots
     const int lane = threadIdx.x & 63;
-    double* sYw = sY + (size_t)(threadIdx.x >> 6) * (rows_alloc * GRAM_LD + GRAM_TAIL);
+    const int slice_len = rows_alloc * GRAM_LD + GRAM_TAIL + (SPLIT ? GRAM_VEC : 0);
+    double* sYw = sY + (size_t)(threadIdx.x >> 6) * slice_len;
     double* sCam = sYw + rows_alloc * GRAM_LD;
     double* sScale = sCam + GRAM_KMAX * GRAM_CAMREC;                     // [DC K] Jacobi scale of Gram row DC k + d
     int* sSlot = (int*)(sScale + 48);                                    // [GRAM_NPAIR] pair slots, then [GRAM_KMAX] diagonal blocks
@@ -827,6 +837,11 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
     const int* rec = gr_rec + (size_t)task * GRAM_REC;                   // one record per task (ba_flatten.h): wave-uniform, scalar loads
     const int p0 = __builtin_amdgcn_readfirstlane(rec[0]), cnt = __builtin_amdgcn_readfirstlane(rec[1]), K = __builtin_amdgcn_readfirstlane(rec[2]);
     const int j00 = __builtin_amdgcn_readfirstlane(rec[3]);
+    int s_begin = 0, s_end = cnt;                                        // this wave's share of the task's points (SPLIT: whole sub-chunks, gram_share.h)
+    if constexpr (SPLIT) {
+        gram_share(cnt, (int)(blockDim.x >> 6), __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), s_begin, s_end);
+        s_begin = __builtin_amdgcn_readfirstlane(s_begin); s_end = __builtin_amdgcn_readfirstlane(s_end);
+    }
     const double f = focal[0];
     const int camv = rec[4 + (lane & (GRAM_KMAX - 1))];                 // the task's cameras as a lane vector (gram_cam_of)
     gram_gather<33, GRAM_CAMREC, 6>(cam, rot, camv, K, lane, sCam);
@@ -840,8 +855,8 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
         // ---- the point pass of the task's points (k_point_lin), before the camera sums and the tile accumulators are alive
         constexpr int KC = ((16 * NT + (TI > 0 ? 4 : 0)) / DC < GRAM_KMAX) ? (16 * NT + (TI > 0 ? 4 : 0)) / DC : GRAM_KMAX;      // the longest camera list of this tile class
         wave_lds_handover();                                             // sCam is written
-        for (int r0 = 0; r0 < cnt; r0 += 64) {
-            const bool valid = r0 + lane < cnt;
+        for (int r0 = s_begin; r0 < s_end; r0 += 64) {                   // (SPLIT: the points of this wave's share only -- the loop reads back what this wave stored)
+            const bool valid = r0 + lane < s_end;
             const int q = min(r0 + lane, cnt - 1);                       // (past the end: the last point again, nothing stored, nothing summed)
             const size_t p = (size_t)(p0 + q);
             const double2* op = obs_xy + (j00 + (size_t)q * K);
@@ -903,7 +918,7 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
             pgmax = wave_max(pgmax);
             const int slot = wave_tr_index();
             double* sl = fz.scal + (size_t)(task & (SC_NSLOT - 1)) * SC_TOTAL;
-            if (slot < 5) unsafeAtomicAdd(&sl[slot], t);
+            if (slot < 5 && (!SPLIT || s_begin < s_end)) unsafeAtomicAdd(&sl[slot], t);
             if (lane == 0 && pgmax > 0.0) atomic_max_nonneg(&sl[SC_GMAX], pgmax);
         }
         // the loop below reads PS back on other lanes of this wave: the stores have left before the first load is issued
@@ -936,9 +951,9 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
         if (focal_free) { _Pragma("unroll") for (int k = 9; k < 12; k++) V[k] = PSr[12 * (size_t)(p0 + q_) + k]; }                \
         ob = obs_xy[j00 + (size_t)q_ * K + kq];                                                                                   \
     } while (0)
-    GRAM_LOAD(0);
+    GRAM_LOAD(s_begin);
     long long t_1 = 0, t_2 = 0;
-    for (int s0 = 0; s0 < cnt; s0 += GRAM_SUB) {
+    for (int s0 = s_begin; s0 < s_end; s0 += GRAM_SUB) {
         wave_lds_handover();                                             // the tiles of the previous sub-chunk have read sY (first pass: sCam is written)
         {
             const bool valid = s0 + lp < cnt;
@@ -1000,7 +1015,7 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
             }
         }
         if (dbg && s0 == 0) t_1 = wall_clock64();                       // first sub-chunk linearised
-        if (s0 + GRAM_SUB < cnt) GRAM_LOAD(s0 + GRAM_SUB);              // in flight while the tiles run
+        if (s0 + GRAM_SUB < s_end) GRAM_LOAD(s0 + GRAM_SUB);              // in flight while the tiles run
         wave_lds_handover();
         // tiles of the lower triangle: G(ti, tj) += Y(ti rows) Y(tj rows)^T over the 24 columns of this sub-chunk, 4 per instruction
         // (only the row tiles that hold cameras: the tasks are sorted by K and every tile count has its own launch -- DC K <= 16: one product per k-step,
@@ -1084,10 +1099,21 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
             const int c = cam_k;
             const double* sc = sScale + DC * lq;
             const int i0 = 4 * (lane & 1) + 2 * ((lane >> 1) & 1) + ((lane >> 2) & 1);
+            double* vec = sYw + rows_alloc * GRAM_LD + GRAM_TAIL + lq * 4 * DC;      // (SPLIT: this wave's vectors of camera lq, summed over the slices behind the barrier)
 #pragma unroll
             for (int j = 0; j < NO; j++) {
                 const int i = 8 * j + i0;
                 const double v = out[j];
+                if constexpr (SPLIT) {
+                    if (i < NU) {
+                        int a = 0, rem = i; while (rem >= DC - a) { rem -= DC - a; a++; }
+                        const int b = a + rem;
+                        const double w = v * sc[a] * sc[b];
+                        sG[g_off(DC * lq + b) + DC * lq + a] += w;
+                        if (b == a) vec[a] = w;
+                    } else if (i < NU + 2 * DC) vec[DC + (i - NU)] = v * sc[(i - NU) % DC];
+                    else if (i < NS) vec[3 * DC + (i - NU - 2 * DC)] = v * sc[i - NU - 2 * DC];      // (zeros when the focal is fixed)
+                } else
                 if (i < NU) {
                     int a = 0, rem = i; while (rem >= DC - a) { rem -= DC - a; a++; }
                     const int b = a + rem;                                // b >= a: the entry (row DC lq + b, column DC lq + a) of the lower triangle
@@ -1099,6 +1125,55 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
                 else if (i < NS && focal_free) { const int a = i - NU - 2 * DC; if (PV) PV[lq * 5 * DC + 4 * DC + a] = v * sc[a]; else zadd(dz, &Sfc[c * DC + a], v * sc[a]); }
             }
         }
+    }
+    if constexpr (SPLIT) {
+        // every wave of the workgroup comes here (the early exits above are uniform over the workgroup; a wave with an empty share has written zeros): the slices
+        // are complete behind the barrier and nobody writes LDS any more.  Slots and orientation come from the wave's own copy of the task's record.
+        __syncthreads();
+        const int W = blockDim.x >> 6, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        auto over_slices = [&](int o) { double v = sY[o]; for (int s = 1; s < W; s++) v += sY[(size_t)s * slice_len + o]; return v; };      // in slice order
+        // the cameras' vectors, once per task: entry (k, which, a) of the W stashes
+        for (int idx = threadIdx.x; idx < K * 4 * DC; idx += blockDim.x) {
+            const int k = idx / (4 * DC), r = idx - k * 4 * DC, which = r / DC, a = r - which * DC;
+            if (which == 3 && !focal_free) continue;
+            const int c = rec[4 + k];
+            const double v = over_slices(rows_alloc * GRAM_LD + GRAM_TAIL + idx);
+            if (which == 0) zadd(dz, &Udiag[c * DC + a], v);
+            else if (which == 1) {                                       // Jc^T r: the raw gradient, and into rhs together with the coupling term
+                zadd(dz, &gcraw[c * DC + a], v);
+                zadd(dz, &rhs[c * DC + a], v + over_slices(rows_alloc * GRAM_LD + GRAM_TAIL + idx + DC));
+            } else if (which == 3) zadd(dz, &Sfc[c * DC + a], v);
+        }
+        if constexpr (2 * BB > 64) {                                     // a block per instruction (see below), the blocks dealt round-robin over the waves
+            const int e = min(lane, BB - 1), da = e / DC, db = e - da * DC, eT = db * DC + da;
+            const bool on = lane < BB;
+            int turn = 0;
+            for (int a = 0; a < K; a++) {
+                const int Ra = DC * a + da;
+                for (int b = 0; b <= a; b++) {
+                    const bool mine = turn == w; turn = (turn + 1 == W) ? 0 : turn + 1;
+                    if (!mine) continue;
+                    const int C = DC * b + db;
+                    const double v = over_slices((b < a) ? g_off(Ra) + C : g_off(max(Ra, C)) + min(Ra, C));
+                    const int sl = (b < a) ? sSlot[a * (a - 1) / 2 + b] : sDiag[a];
+                    const int eo = (b < a && (sl & (1 << 30))) ? eT : e;
+                    if (on) zadd(dz, &(S_val + (size_t)(sl & 0x3fffffff) * BB)[eo], v);
+                }
+            }
+        } else {
+            const int nent = (K * (K + 1) / 2) * BB;
+            for (int idx = threadIdx.x; idx < nent; idx += blockDim.x) {
+                const int blk = idx / BB, e = idx - blk * BB, da = e / DC, db = e - da * DC;
+                const int a = (int)((__fsqrt_rn((float)(8 * blk + 1)) - 1.0f) * 0.5f);
+                const int b = blk - a * (a + 1) / 2;
+                const int R = DC * a + da, C = DC * b + db;
+                const double v = over_slices(g_off(max(R, C)) + min(R, C));
+                const int sl = (b < a) ? sSlot[a * (a - 1) / 2 + b] : sDiag[a];
+                const int eo = (b < a && (sl & (1 << 30))) ? (db * DC + da) : e;
+                zadd(dz, &(S_val + (size_t)(sl & 0x3fffffff) * BB)[eo], v);
+            }
+        }
+        return;
     }
     wave_lds_handover();
     if constexpr (2 * BB > 64) {
@@ -1149,6 +1224,18 @@ k_schur_gram(const double* __restrict__ cam, const double* __restrict__ rot, con
     const int task = task0 + __builtin_amdgcn_readfirstlane(xcd_contiguous_block(blockIdx.x, gridDim.x) * (blockDim.x >> 6) + (threadIdx.x >> 6));   // [task0, ntasks): this launch's tile class
     if (task >= ntasks) return;
     schur_gram_task<DC, NT, TI, FUSE>(cam, rot, pts, focal, obs_xy, gr_rec, scale_cam, scale_f, PS, loss, la, rows_alloc, focal_free, task, S_val, rhs, Udiag, Sfc, gcraw, dbg, fz, dz);
+}
+// Round 11: ONE task per workgroup, shared by its blockDim.x / 64 = 2 .. 4 waves (schur_gram_task: SPLIT) -- the launch of a problem with fewer tasks than the chip
+// holds waves of this kernel (ba_solver.hip: LmRun::gram_split).  Same arguments, same tile classes; dynamic LDS = a slice + GRAM_VEC doubles per wave.
+template <int DC, int NT, int TI = 0, bool FUSE = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
+k_schur_gram_split(const double* __restrict__ cam, const double* __restrict__ rot, const double* __restrict__ pts, const double* __restrict__ focal,
+                   const double2* __restrict__ obs_xy, int ntasks, const int* __restrict__ gr_rec, const double* __restrict__ scale_cam, const double* __restrict__ scale_f,
+                   const double* __restrict__ PS, int loss, double la, int rows_alloc, int focal_free, int task0, double* __restrict__ S_val, double* __restrict__ rhs,
+                   double* __restrict__ Udiag, double* __restrict__ Sfc, double* __restrict__ gcraw, long long* __restrict__ dbg, GramFuse fz = GramFuse{}, DetZone dz = DetZone{}) {
+    const int task = task0 + __builtin_amdgcn_readfirstlane(xcd_contiguous_block(blockIdx.x, gridDim.x));
+    if (task >= ntasks) return;                                          // uniform over the workgroup, like every exit in front of the task's barrier
+    schur_gram_task<DC, NT, TI, FUSE, true>(cam, rot, pts, focal, obs_xy, gr_rec, scale_cam, scale_f, PS, loss, la, rows_alloc, focal_free, task, S_val, rhs, Udiag, Sfc, gcraw, dbg, fz, dz);
 }
 // Round 5: ALL tile classes in one launch -- tracks of mixed length (a real sequence: 3 ... 8 cameras per point) gave one launch per class, each with the ~25 us latency
 // floor of a wave task, one after the other on the stream (4 x 25 us against 44 + 21 us through the pair lists: the planner refused the groups, profiles/r04_notes.md

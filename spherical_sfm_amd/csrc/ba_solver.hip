@@ -57,6 +57,7 @@ struct LmRun {
     const bool phases;
     // the knobs of a solve (read_knobs)
     bool poll = false, spec_on = false, fuse_lin = false; int gram_bs = -1, gbs_split_env = 0;
+    int gram_split[5] = {1, 1, 1, 1, 1};                                 // waves per task of k_schur_gram, per tile class (read_knobs)
     double *host_scal = nullptr, *host_pcg1 = nullptr;               // the iteration's scalars and solver flags as the host reads them
     // trust region
     double radius, decrease_factor = 2.0, x_norm = 0.0, x_cost = 0.0, minimum_cost = std::numeric_limits<double>::max();
@@ -158,7 +159,27 @@ struct LmRun {
         // SSFM_DETERMINISTIC=1 (the fused epilogue adds its sums with plain atomics).  SSFM_GRAM_FUSE=0: k_point_lin + the unfused kernel (profiles/r09_notes.md).
         { int cls_end[5]; const int n_cls = gram_classes(cls_end);
           fuse_lin = knob_env_int("SSFM_GRAM_FUSE", 1) != 0 && !h->det && nP > 0 && !F.gr_rec.empty() && F.gram_points == (int64_t)nP && F.chunk_cam.empty() && F.cs_task_cam.empty()
-                     && !(F.gram_any && n_cls > 1) && cls_end[4] == cls_end[3]; }      // (no task of the three-tile class: gram_kernel_of)
+                     && !(F.gram_any && n_cls > 1) && cls_end[4] == cls_end[3];      // (no task of the three-tile class: gram_kernel_of)
+          // Waves per task of k_schur_gram (ba_kernels.h: SPLIT).  A wave of it takes half a SIMD's registers, so the chip holds 8 waves per CU: a launch with fewer
+          // tasks than that gives every task W of them, W <= 4 and at most one per sub-chunk of the launch's longest task (config 2: 900 tasks -> 2; <= 512 -> 4;
+          // the configs[4] size, thousands of tasks -> 1 = the unsplit kernel).  SSFM_GRAM_SPLIT=1..4 forces W.  SSFM_DETERMINISTIC=1 keeps W = 1 whatever the knob
+          // says: its per-task partial buffer takes plain stores of ONE wave per task (det_acc.h), and the limbs' order independence is tested on the unsplit kernel.
+          const int split_env = knob_env_int("SSFM_GRAM_SPLIT", 0);
+          const bool unsplit = h->det || SSFM_LAB_KNOB("SSFM_GRAM_WAVES", 1) != 1 || SSFM_LAB_KNOB("SSFM_GRAM_EMIT_SKIP", 0) != 0 || SSFM_LAB_KNOB("SSFM_GRAM_STAMPS", 0) != 0
+                               || (F.gram_any && n_cls > 1);             // (the lab shapes and the mixed-class launch k_schur_gram_any stay unsplit)
+          for (int cl = 0; cl < 5; cl++) {
+              const int t0 = cl ? cls_end[cl - 1] : 0, t1 = cls_end[cl];
+              gram_split[cl] = 1;
+              if (t1 <= t0 || unsplit) continue;
+              int max_sub = 1;
+              for (int t = t0; t < t1; t++) max_sub = std::max(max_sub, (F.gr_rec[(size_t)t * GRAM_REC + 1] + GRAM_SUB_PTS - 1) / GRAM_SUB_PTS);
+              // a workgroup lives on ONE CU: 8 / W of them fit there, so 4 waves per task while the tasks fit 2 per CU, 2 while they fit 4 per CU (3 holds no more
+              // workgroups per CU than 4 does: 600 tasks x 3 waves ran in two rounds, 58.6 us against 51.8 with 2 -- profiles/r11_notes.md)
+              const int ntask = t1 - t0, by_count = ntask <= 2 * ctx->num_cus ? 4 : ntask <= 4 * ctx->num_cus ? 2 : 1;
+              gram_split[cl] = (split_env >= 1 && split_env <= 4) ? split_env : std::min(max_sub, by_count);
+              if (std::getenv("SSFM_PLAN_TIMING")) std::fprintf(stderr, "[solve] gram split: class %d, %d tasks, longest %d sub-chunks: %d waves per task\n", cl, t1 - t0, max_sub, gram_split[cl]);
+          }
+        }
         return SSFM_OK;
     }
 
@@ -259,7 +280,16 @@ struct LmRun {
         static const GramKernel k[5] = {k_schur_gram<DC, 1, 0, FUSE>, k_schur_gram<DC, 1, 2, FUSE>, k_schur_gram<DC, 2, 0, FUSE>, k_schur_gram<DC, 2, 3, FUSE && DC == 6>, k_schur_gram<DC, 3, 0, false>};
         return k[cls];
     }
-    GramKernel gram_kernel(int cls) const { return fuse_lin ? gram_kernel_of<true>(cls) : gram_kernel_of<false>(cls); }
+    // the same classes with the task shared by the waves of a workgroup (3-dof cameras: three classes, launch_gram asks for no other)
+    template <bool FUSE> static GramKernel gram_split_kernel_of(int cls) {
+        static const GramKernel k[5] = {k_schur_gram_split<DC, 1, 0, FUSE>, k_schur_gram_split<DC, 1, 2, FUSE>, k_schur_gram_split<DC, 2, 0, FUSE>,
+                                        DC == 6 ? k_schur_gram_split<6, 2, 3, FUSE> : nullptr, DC == 6 ? k_schur_gram_split<6, 3, 0, false> : nullptr};
+        return k[cls];
+    }
+    GramKernel gram_kernel(int cls, bool split) const {
+        if (split) return fuse_lin ? gram_split_kernel_of<true>(cls) : gram_split_kernel_of<false>(cls);
+        return fuse_lin ? gram_kernel_of<true>(cls) : gram_kernel_of<false>(cls);
+    }
     // one launch per tile class (the tasks are sorted by K, i.e. by rows = DC K): rows <= 16 -> 1 row tile of 16; 17..20 -> 1 tile + a tail of <= 4 rows through
     // the 4x4x4 instruction; <= 32 -> 2 tiles; 33..36 -> 2 tiles + tail; else 3 tiles.  cls_end[cl] = end of class cl's task range; returns the classes in use
     static bool gram_t4() { return SSFM_LAB_KNOB("SSFM_GRAM_T4", 1) != 0; }
@@ -296,11 +326,14 @@ struct LmRun {
             for (int cl = 0; cl < (DC == 6 ? 5 : 3); cl++) {              // (3-dof cameras: two row tiles at most)
                 const int t0 = cl ? cls_end[cl - 1] : 0, t1 = cls_end[cl];
                 if (t1 <= t0) continue;
-                const GramKernel kernel = gram_kernel(cl);
+                // W > 1: one task per workgroup, shared by its W waves, a slice of LDS (+ the vectors' stash) each; else gram_waves tasks per workgroup, a wave each
+                const int W = (gram_waves == 1 && !gram_dbg && !fz.emit_skip) ? gram_split[cl] : 1;
+                const GramKernel kernel = gram_kernel(cl, W > 1);
                 const int rows_alloc = DC * F.gr_rec[(size_t)(t1 - 1) * GRAM_REC + 2];              // the largest K of the class: its last task
-                const size_t gram_lds = (size_t)gram_waves * ((size_t)rows_alloc * GRAM_LD + GRAM_TAIL) * sizeof(double);
+                const size_t gram_lds = W > 1 ? (size_t)W * ((size_t)rows_alloc * GRAM_LD + GRAM_TAIL + GRAM_VEC) * sizeof(double)
+                                              : (size_t)gram_waves * ((size_t)rows_alloc * GRAM_LD + GRAM_TAIL) * sizeof(double);
                 if (gram_lds > 48 * 1024) SSFM_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_lds));
-                LAUNCH(h, KID_SCHUR_GRAM, kernel, (t1 - t0 + gram_waves - 1) / gram_waves, 64 * gram_waves, gram_lds, at.cam, at.rot, at.pts, at.focal, oxy, t1, h->gr_rec.p,
+                LAUNCH(h, KID_SCHUR_GRAM, kernel, W > 1 ? t1 - t0 : (t1 - t0 + gram_waves - 1) / gram_waves, W > 1 ? 64 * W : 64 * gram_waves, gram_lds, at.cam, at.rot, at.pts, at.focal, oxy, t1, h->gr_rec.p,
                        h->scale_cam.p, h->scale_f.p, h->Vs.p, loss, la, rows_alloc, F.focal_free ? 1 : 0, t0, z.S_val, z.rhs, z.Udiag, z.Sfc, z.gcraw, gram_dbg, fz, z.det);
             }
         }
