@@ -11,6 +11,7 @@
 #include "ba_flatten.h"
 #include "band_kernels3.h"
 #include "band_kernels2p.h"
+#include "band_back_lds.h"
 using namespace ssfm;
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(1); } } while (0)
 

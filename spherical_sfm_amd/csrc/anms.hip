@@ -20,7 +20,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <cstring>
-#include "ba_handle.h"
+#include "dev_buf.h"
 #include "anms_host.h"
 
 namespace ssfm {

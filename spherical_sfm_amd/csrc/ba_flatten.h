@@ -245,7 +245,7 @@ inline int cuthill_mckee(int n, const std::vector<int>& row_ptr, const std::vect
 // Elimination order seg_0 | seg_1 reversed | sep; band rows seg_0 | sep | seg_1 reversed | copy of sep.
 // A component is twisted when both segments are longer than the band (n >= 3 b + 2) and it is not long enough to be cut into
 // several segments (band_sub.h, SUB_MIN_ROWS); the kernels involved need the LDS-resident factorisation (b <= 20).
-// Half-widths above 20 (6x6 blocks) need the packed-window factorisation (band_kernels2p.h, ba_handle.h: band_wide_packed): with it on (default) components are
+// Half-widths above 20 (6x6 blocks) need the packed-window factorisation (band_kernels2p.h, band_path.h: band_wide_packed): with it on (default) components are
 // twisted up to half-width 30, with SSFM_BAND_PACKED=0 up to 20 as before (the global-memory kernels that then serve wide bands know no twisted layout).
 inline bool band_packed_enabled() { const char* e = std::getenv("SSFM_BAND_PACKED"); return !(e && std::atoi(e) == 0); }
 inline int band_wide_max() { return band_packed_enabled() ? 30 : 20; }

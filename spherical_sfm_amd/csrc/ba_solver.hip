@@ -24,7 +24,7 @@
 #include "knobs.h"
 #include "ssfm_ctx.h"
 
-#include "ba_handle.h"
+#include "reduced_solve.h"
 
 namespace ssfm {
 

@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ba_kernels.h"
+#include "band_path.h"
 
 namespace ssfm {
 
@@ -284,7 +285,7 @@ __global__ void __launch_bounds__(1024)
 k_band_chol(double* __restrict__ band, double* __restrict__ Linv_out, double* __restrict__ Y, const int* __restrict__ pairs,
             int N, int b, int* __restrict__ fail_flag) {
     constexpr int BB = DC * DC;
-    extern __shared__ __attribute__((aligned(16))) double lds[];
+    extern __shared__ __attribute__((aligned(16))) double lds[];      // carve-up = band_chol_lds_bytes (band_path.h)
     double* sLinv = lds;                // BB
     double* sDiag = lds + BB;           // BB
     double* sY = sDiag + BB;            // NR*DC
@@ -394,7 +395,7 @@ template <int DC, int NR>
 __global__ void __launch_bounds__(256)
 k_band_fwd(const double* __restrict__ band, const double* __restrict__ Linv, double* __restrict__ Y, int N, int b) {
     constexpr int BB = DC * DC;
-    extern __shared__ __attribute__((aligned(16))) double lds[];
+    extern __shared__ __attribute__((aligned(16))) double lds[];      // carve-up = band_subst_lds_bytes (band_path.h)
     double* sX = lds;                       // ring of the last b solutions: [b][NR*DC]
     double* sPart = sX + (size_t)b * NR * DC;   // [b][NR*DC] partial products
     double* sAcc = sPart + (size_t)b * NR * DC; // NR*DC
@@ -435,7 +436,7 @@ template <int DC, int NR>
 __global__ void __launch_bounds__(256)
 k_band_back(const double* __restrict__ band, const double* __restrict__ Linv, double* __restrict__ Y, int N, int b) {
     constexpr int BB = DC * DC;
-    extern __shared__ __attribute__((aligned(16))) double lds[];
+    extern __shared__ __attribute__((aligned(16))) double lds[];      // carve-up = band_subst_lds_bytes (band_path.h)
     double* sX = lds;
     double* sPart = sX + (size_t)b * NR * DC;
     double* sAcc = sPart + (size_t)b * NR * DC;
@@ -567,83 +568,19 @@ k_ref_step(const double* __restrict__ Sfc, const double* __restrict__ Sff, int N
 }  // namespace ssfm
 
 // =====================================================================================================
-// Substitution kernels for factors produced by k_band_chol_v2 (band_kernels2.h): one workgroup per connected component of
-// the camera graph (comp_ptr: contiguous position ranges from the Cuthill-McKee pass).  The forward kernel serves the PCG
-// refinement path; the back kernel is the fallback for bands too wide for the single-wave k_band_back_v2.
+// Forward substitution for factors produced by k_band_chol_v2 (band_kernels2.h): one workgroup per connected component of
+// the camera graph (comp_ptr: contiguous position ranges from the Cuthill-McKee pass), for the PCG refinement path.  (Its back-substitution
+// twin, k_band_back_lds, is scripts/lab/band_back_lds.h: every band with an LDS-resident factor takes the single-wave k_band_back_v2.)
 // =====================================================================================================
 namespace ssfm {
 
-// back substitution Y <- L^-T Y per component; next column of L prefetched into registers while the current step runs
-template <int DC, int NR>
-__global__ void __launch_bounds__(256)
-k_band_back_lds(const double* __restrict__ band, const double* __restrict__ Linv, double* __restrict__ Y, const int* __restrict__ comp_ptr,
-                int N, int b) {
-    constexpr int BB = DC * DC;
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    double* sX = lds;                               // ring [b][NR*DC]
-    double* sPart = sX + (size_t)b * NR * DC;       // [b][NR*DC]
-    double* sAcc = sPart + (size_t)b * NR * DC;     // NR*DC
-    const int W = b + 1, n = N * DC, tid = threadIdx.x;
-    const int r0 = comp_ptr[blockIdx.x], r1 = comp_ptr[blockIdx.x + 1];
-    const int d = tid / DC + 1, a = tid - (d - 1) * DC;     // this lane's (offset, column) of the L column, valid if tid < b*DC
-    const bool has = tid < b * DC;
-    double col[DC], li[DC], yv = 0.0;
-    auto fetch = [&](int j) {
-#pragma unroll
-        for (int m = 0; m < DC; m++) col[m] = (has && j >= r0 && j + d < r1) ? band[(((size_t)(j + d)) * W + d) * BB + m * DC + a] : 0.0;
-        if (tid < NR * DC && j >= r0) {
-            const int aa = tid % DC;
-#pragma unroll
-            for (int k = 0; k < DC; k++) li[k] = (k >= aa) ? Linv[(size_t)j * BB + k * DC + aa] : 0.0;      // column aa of L_jj^-1 = row of L^-T
-            yv = Y[(size_t)(tid / DC) * n + (size_t)j * DC + aa];
-        }
-    };
-    fetch(r1 - 1);
-    int jm = (b > 0) ? (r1 - 1) % b : 0;                     // ring slot of row j, kept incrementally
-    for (int j = r1 - 1; j >= r0; j--, jm = (jm == 0) ? max(b - 1, 0) : jm - 1) {
-        const int nb = min(b, r1 - 1 - j);
-        double cur[DC], curli[DC]; const double cury = yv;
-#pragma unroll
-        for (int m = 0; m < DC; m++) { cur[m] = col[m]; curli[m] = li[m]; }
-        fetch(j - 1);                                   // in flight during this step
-        if (has && d <= nb) {
-#pragma unroll
-            for (int r = 0; r < NR; r++) {
-                const int xs = (jm + d >= b) ? jm + d - b : jm + d;
-                const double* x = sX + ((size_t)xs * NR + r) * DC;
-                double s = 0.0;
-#pragma unroll
-                for (int m = 0; m < DC; m++) s += cur[m] * x[m];
-                sPart[((size_t)(d - 1) * NR + r) * DC + a] = s;
-            }
-        }
-        lds_barrier();
-        if (tid < NR * DC) {
-            const int r = tid / DC, aa = tid - r * DC;
-            double s = cury;
-            for (int dd = 0; dd < nb; dd++) s -= sPart[((size_t)dd * NR + r) * DC + aa];
-            sAcc[tid] = s;
-        }
-        lds_barrier();
-        if (tid < NR * DC) {
-            const int r = tid / DC, aa = tid - r * DC;
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < DC; k++) s += curli[k] * sAcc[r * DC + k];
-            Y[(size_t)r * n + (size_t)j * DC + aa] = s;
-            if (b > 0) sX[((size_t)jm * NR + r) * DC + aa] = s;
-        }
-        lds_barrier();
-    }
-}
-
-// forward substitution Y <- L^-1 Y per component with the same prefetch scheme (PCG refinement applications)
+// forward substitution Y <- L^-1 Y per component, the next row of L prefetched into registers while the current step runs (PCG refinement applications)
 template <int DC, int NR>
 __global__ void __launch_bounds__(256)
 k_band_fwd_lds(const double* __restrict__ band, const double* __restrict__ Linv, double* __restrict__ Y, const int* __restrict__ comp_ptr,
                int N, int b) {
     constexpr int BB = DC * DC;
-    extern __shared__ __attribute__((aligned(16))) double lds[];
+    extern __shared__ __attribute__((aligned(16))) double lds[];      // carve-up = band_subst_lds_bytes (band_path.h)
     double* sX = lds;
     double* sPart = sX + (size_t)b * NR * DC;
     double* sAcc = sPart + (size_t)b * NR * DC;

@@ -14,6 +14,7 @@
 #pragma once
 #include <type_traits>
 #include "band_kernels.h"
+#include "band_path.h"
 
 namespace ssfm {
 
@@ -67,40 +68,7 @@ __device__ __forceinline__ bool wave_chol_inverse(double (&row)[DC], double (&g)
 //                               only waves that ever wait on vmcnt
 //   last wave                   writer: panel, y_j and G to global memory (stores only, never waited on)
 // Every wave takes its share of the panel product in phase B.
-constexpr int CHOL2_LOADERS = 2;
-// Role of every PHYSICAL wave of the workgroup (wave p runs on SIMD p % 4): v[p] = the role index the kernel's logic uses (0 look-ahead,
-// 1..ntw trailing update, then the loaders, the writer last).  With the identity a nine-wave workgroup puts the look-ahead (the dependent chain of
-// the step), a trailing wave and the writer on SIMD 0: their phases took 1.6k / 2.2k / 2.1k cycles against 1.3-1.5k for the trailing waves
-// that share a SIMD with one loader only, and the step waits for the slowest (s_memtime stamps, scripts/lab/chol_stamps.hip).
-struct CholWaveMap { unsigned char v[16]; };
-inline CholWaveMap chol_wave_map(int nw, int ntw, int heavy_tw) {      // heavy_tw: trailing waves that carry block tasks (the rest only right-hand sides)
-    CholWaveMap m; for (int i = 0; i < 16; i++) m.v[i] = (unsigned char)i;
-    // Measured, not derived: the nine-wave workgroup of config 2 (6x6 blocks, half-width 10) gains 18 % per step; with eleven waves (half-width 14,
-    // where both loaders then sit with the look-ahead: 286 -> 340 us per launch at the configs[4] size) and with six (merged 3-dof pairs: 2.18 -> 2.20 ms per
-    // solve) the identity is better, so only the shape that was stamped is remapped.
-    if (nw != 9) return m;
-    int weight[16], order[16];
-    for (int r = 0; r < nw; r++) {
-        weight[r] = (r == 0) ? 12 : (r <= ntw) ? ((r <= heavy_tw) ? 6 : 2) : (r == nw - 1) ? 5 : 4;
-        order[r] = r;
-    }
-    for (int a = 0; a < nw; a++) for (int c = a + 1; c < nw; c++) if (weight[order[c]] > weight[order[a]]) { const int t = order[a]; order[a] = order[c]; order[c] = t; }
-    int load[4] = {0, 0, 0, 0}, used[4] = {0, 0, 0, 0}, cap[4];
-    for (int q = 0; q < 4; q++) cap[q] = (nw - q + 3) / 4;                // physical waves q, q + 4, ...
-    // SIMD 0: the look-ahead (first in the order) and the LIGHTEST roles for its other waves; everything else heaviest first onto the least
-    // loaded of the other three SIMDs
-    bool placed[16] = {false};
-    m.v[0] = (unsigned char)order[0]; placed[0] = true; used[0] = 1;
-    for (int a = nw - 1; a >= 1 && used[0] < cap[0]; a--) { m.v[4 * used[0]] = (unsigned char)order[a]; placed[a] = true; used[0]++; }
-    for (int a = 1; a < nw; a++) {
-        if (placed[a]) continue;
-        int best = -1;
-        for (int q = 1; q < 4; q++) if (used[q] < cap[q] && (best < 0 || load[q] < load[best])) best = q;
-        m.v[best + 4 * used[best]] = (unsigned char)order[a];
-        load[best] += weight[order[a]]; used[best]++;
-    }
-    return m;
-}
+// CHOL2_LOADERS and the table that deals the roles to the physical waves (CholWaveMap, chol_wave_map): band_path.h
 
 // MF = true (DC = 6 only): the panel product and the trailing update run on the matrix cores -- v_mfma_f64_16x16x4_f64 tiles in
 // window-relative coordinates (row i of the window = block i / 6 + 1 behind the pivot, scalar row i % 6), K = the pivot's six columns in two
@@ -200,12 +168,13 @@ k_band_chol_v2(double* __restrict__ band, double* __restrict__ Ginv, double* __r
                const int* __restrict__ piv_lo, const int* __restrict__ piv_hi, const int* __restrict__ win_hi,
                const int* __restrict__ merge_from, int N, int b, int* __restrict__ fail_flag,
                const CholWaveMap wmap,                 // role of every physical wave (chol_wave_map; identity = roles in wave order)
-               // fused launch of segments and the separators that wait for them (ba_handle.h band_direct): per workgroup the first of two flags to await
+               // fused launch of segments and the separators that wait for them (reduced_solve.h band_substructured): per workgroup the first of two flags to await
                // before its window is loaded (-1: none) and the flag to raise when its rows are in global memory (-1: none); flags hold launch numbers
                const int* __restrict__ await2 = nullptr, const int* __restrict__ signal = nullptr, int* __restrict__ flags = nullptr, int seq = 0) {
     constexpr int BB = DC * DC;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int R = b + 1, W = b + 1, RW = W * BB;
+    // carve-up = chol2_lds_bytes (band_path.h)
     double* sWin = lds;                                     // [R][W][BB] ring of window rows
     double* sP = sWin + (size_t)R * RW;                     // [b][BB]    panel of the current step = L(j+k, j)
     double* sYr = sP + (size_t)b * BB;                      // [R][NR][DC] right-hand-side rows of the window
@@ -296,7 +265,7 @@ k_band_chol_v2(double* __restrict__ band, double* __restrict__ Ginv, double* __r
     const int lw = wave - 1 - ntw;                          // loader index, valid when 0 <= lw < CHOL2_LOADERS
     // ---- phase B, shared by every role: panel X_k = A_k G^T and y_j = G y_j into LDS
     const int li = lane & 15, lk = lane >> 4;
-    // round 4: when every panel entry has a thread of its own (b BB <= threads: always in the shapes ba_handle.h launches) the entry's coordinates are the same in
+    // round 4: when every panel entry has a thread of its own (b BB <= threads: always in the shapes band_path.h plans) the entry's coordinates are the same in
     // every step -- two integer divisions and the address arithmetic leave the step loop (a step is ~10 ticks per instruction on every wave: profiles/r04_notes.md)
     // MF bit 2 (round 4, "early look-ahead"): the look-ahead wave keeps block 0 of the panel (X_1, 36 entries) for itself and has it -- and with it the update of the
     // next diagonal block -- done BEFORE barrier A, while the other waves compute the rest of the panel; its part after the barrier is the factorisation alone.
@@ -504,7 +473,7 @@ k_band_chol_v2(double* __restrict__ band, double* __restrict__ Ginv, double* __r
                 lds_barrier();
             }
         } else {
-        // round 4: with one block task per lane (the shapes ba_handle.h launches) the lane's task is the same in every step: its pair (an LDS round trip on the
+        // round 4: with one block task per lane (the shapes band_path.h plans) the lane's task is the same in every step: its pair (an LDS round trip on the
         // dependent path of the phase), tile coordinates and operand offsets are fixed before the loop
         const int own_t = ct + TPB, own_pr = min(own_t / TPB, b * (b + 1) / 2 - 1), own_sub = own_t - (own_t / TPB) * TPB;
         const int own_pk = sPairs[own_pr], own_ir = own_pk & 0xffff, own_kr = own_pk >> 16;

@@ -21,11 +21,6 @@ namespace ssfm {
 
 __device__ __host__ __forceinline__ int win2p_base(int d, int b) { return d * (b + 1) - d * (d - 1) / 2; }
 __device__ __forceinline__ int win2p_slot(int i, int d, int b) { return win2p_base(d, b) + i % (b + 1 - d); }
-inline size_t chol2p_lds_bytes(int b, int NR, bool t6 = false) {
-    constexpr int DC = 6, BB = 36;
-    return ((size_t)(b + 1) * (b + 2) / 2 * BB + (size_t)b * BB * (t6 ? 2 : 1) + (size_t)(b + 1) * NR * DC + NR * DC + 2 * BB) * sizeof(double) + ((size_t)b * (b + 1) / 2 + 2) * sizeof(int);
-}
-
 //   band / Ginv / Y / pairs / piv_lo / piv_hi / win_hi / merge_from / await2 / signal / flags: exactly as k_band_chol_v2.
 // blockDim.x = 64 * (1 + ntw + 2 + 1), ntw trailing waves with NTASK * 64 * ntw >= 4 (b (b+1) / 2 - 1) + 6 b; NPB * blockDim.x >= 36 b;
 // PRE * 128 >= 36 (b+1) + 6 NR.
@@ -40,6 +35,7 @@ k_band_chol_v2p(double* __restrict__ band, double* __restrict__ Ginv, double* __
     constexpr int DC = 6, BB = 36, LOADERS = 2;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int R = b + 1, RW = R * BB, nslots = R * (R + 1) / 2;
+    // carve-up = chol2p_lds_bytes (band_path.h)
     double* sWin = lds;                                     // [nslots][BB] packed window
     double* sP = sWin + (size_t)nslots * BB;                // [b][BB]    panel of the current step = L(j+k, j)
     double* sYr = sP + (size_t)b * BB;                      // [R][NR][DC] right-hand-side rows of the window (ring)

@@ -26,7 +26,6 @@
 
 namespace ssfm {
 
-constexpr int RING_BACK_P = 8;                    // threads that share one entry of F^T x in ring_back_node
 inline size_t ring_elim_lds_bytes(int Q, int NR) { return (size_t)(3 * Q + NR) * (size_t)(Q | 1) * sizeof(double); }
 
 // one 16x16 tile of P R^T with P, R = rows of the LDS matrix T (row stride LD, odd: the sixteen rows of an operand read fall into sixteen different banks); K = Q columns.
@@ -52,7 +51,7 @@ template <int DC, int NR>
 __device__ __forceinline__ void ring_elim_node(const int* __restrict__ r, const double* __restrict__ Z, const double* __restrict__ Dd, const double* __restrict__ tt,
                                                double* __restrict__ crL, double* __restrict__ crF, double* __restrict__ crW, double* __restrict__ crP, double* __restrict__ crT,
                                                double* __restrict__ crE, const int N, const int b, int* __restrict__ fail_flag, double* __restrict__ T,
-                                               long long* __restrict__ stamps = nullptr,        // stamps: SSFM_RING_STAMPS timing study (ba_handle.h), null otherwise
+                                               long long* __restrict__ stamps = nullptr,        // stamps: SSFM_RING_STAMPS timing study (reduced_solve.h), null otherwise
                                                const int role = 0, const int nroles = 1) {      // r05ag: nroles workgroups per node (below, phase 3)
     const long long ts0 = stamps ? wall_clock64() : 0;
     const int Q = b * DC, LD = Q | 1, n = N * DC, tid = threadIdx.x, nt = blockDim.x, wave = tid >> 6, lane = tid & 63, nw = nt >> 6;

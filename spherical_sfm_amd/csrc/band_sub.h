@@ -134,7 +134,7 @@ inline void sub_build(const std::vector<int>& comp_ptr, const std::vector<char>&
 // wave run one after the other inside a step, and there are CUs to spare -- 4 columns 210 us, 2 columns 169 us, 1 column 130 us per launch at the configs[4] size.
 // Round 5: narrow bands (the ring-native layout halves the half-width) turn the balance again -- the arithmetic of a step shrinks with the band, the factor rows every
 // column streams do not: 42 columns x 102 arcs at the configs[4] size read the whole band 42 times (311 MB from L2, ~72 us whatever the number of arcs).  NC is a template
-// parameter now; the launch picks it by the number of one-wave workgroups it would have (ba_handle.h, r05ac: one column per wave until the chip is full).
+// parameter now; the launch picks it by the number of one-wave workgroups it would have (band_path.h spike_cols, r05ac: one column per wave until the chip is full).
 constexpr int SPIKE_PD = 4, SPIKE_NC = 1;
 template <int DC, int NC = SPIKE_NC>
 __global__ void __launch_bounds__(64)
@@ -401,6 +401,7 @@ k_sub_sep_chain(const double* __restrict__ Z, const double* __restrict__ Dd, con
     extern __shared__ __attribute__((aligned(16))) double lds[];
     constexpr int NB = DC;
     const int Q = b * DC, n = N * DC, tid = threadIdx.x, nt = blockDim.x, NP = Q * (Q + 1) / 2;
+    // carve-up = chain_lds_bytes, one triangle (band_path.h)
     double* sL = lds;                  // [NP]   packed lower triangle, row-major: (i, c) at i(i+1)/2 + c; diagonal blocks hold G = L_blk^-1
     double* sF = sL + NP;              // [Q][Q] column-major: F(i, c) at c*Q + i
     double* sT = sF + (size_t)Q * Q;   // [NR][Q] t_j -> w_j   (backward: v -> x_j)
@@ -690,6 +691,7 @@ k_sub_sep_chain_mfma(const double* __restrict__ Z, const double* __restrict__ Dd
     // pingpong (the host sets it when a second triangle fits the LDS, Q <= 96): two triangles take turns -- the factor of separator j - 1 (read by the F solve of
     // separator j) in one, D_j in the other, and D_{j+1} is brought into the first while separator j is factored: the load of D leaves the dependent chain
     const bool pp = CHAIN_PREFETCH && pingpong != 0;
+    // carve-up = chain_lds_bytes, two triangles with pingpong (band_path.h)
     double* sL = lds;                  // [NP]   packed lower triangle, row-major; the 16x16 diagonal blocks hold G_J = L_JJ^-1
     double* sLp = pp ? lds + NP : lds; // the triangle of the previous separator's factor (the same one without pingpong)
     double* sF = lds + (pp ? 2 : 1) * NP;   // [Q][Q] column-major: F(i, c) at c*Q + i
@@ -1028,7 +1030,6 @@ k_sub_sep_chain_mfma(const double* __restrict__ Z, const double* __restrict__ Dd
 // ---- 5. y(seg) -= Z x(separator in front) ------------------------------------------------------------------------------------------
 // r05ah: 64 rows per workgroup, four threads per row (a quarter of the Q columns each, partial sums through LDS in slice order): one thread per row walked Q loads
 // one after the other -- 11.4 us at Q = 78 for 150 rows per arc.  LDS: NR * Q doubles (x of the separator) + 4 * 64 * NR (partial sums).
-constexpr int APPLY_ROWS = 64, APPLY_SLICES = 4;
 template <int DC, int NR>
 __global__ void __launch_bounds__(APPLY_ROWS * APPLY_SLICES)
 k_sub_apply_left(const double* __restrict__ Z, double* __restrict__ Y, const int* __restrict__ seg_lo, const int* __restrict__ seg_hi,
@@ -1039,7 +1040,7 @@ k_sub_apply_left(const double* __restrict__ Z, double* __restrict__ Y, const int
     if (r0 * DC + (int)blockIdx.y * APPLY_ROWS >= r1 * DC) return;
     const int row = tid & (APPLY_ROWS - 1), slice = tid / APPLY_ROWS;
     const int kk = r0 * DC + blockIdx.y * APPLY_ROWS + row;
-    double* part = lds + NR * Q;                       // [APPLY_SLICES][APPLY_ROWS][NR]
+    double* part = lds + NR * Q;                       // [APPLY_SLICES][APPLY_ROWS][NR]; carve-up = sub_apply_lds_bytes (band_path.h, with APPLY_ROWS / APPLY_SLICES)
     for (int e = tid; e < NR * Q; e += APPLY_ROWS * APPLY_SLICES) { const int r = e / Q, q = e - r * Q; lds[e] = Y[(size_t)r * n + (size_t)(r0 - b) * DC + q]; }
     __syncthreads();
     const int qper = (Q + APPLY_SLICES - 1) / APPLY_SLICES, q0 = slice * qper, q1 = min(Q, q0 + qper);

@@ -10,6 +10,8 @@
 // LAB knobs select a variant that was MEASURED AND REJECTED, a kernel-shape sweep or a timing study (profiles/r0*_notes.md say which): the shipped library compiles
 // their defaults in and does not contain the rejected kernels; `make lab` builds libssfm_hip_lab.so with -DSSFM_LAB, where every one of them is live again
 // (Python: SSFM_LIB_PATH=spherical_sfm_amd/libssfm_hip_lab.so).  SSFM_LAB_KNOB(name, default) is the value, read once per call site.
+// The lab knobs of the reduced solve that change its plan reach band_path.h as a BandPathLab (reduced_solve.h: solve_path fills it); the ones that pick a
+// kernel variant are read inside the launch function of that kernel family (reduced_solve.h).
 #pragma once
 #include <cstddef>
 #include <cstdlib>

@@ -6,7 +6,9 @@
 //   make / decompose_spherical_essential_matrix           src/spherical_utils.cpp:9-66
 // 3x3 matrices are row-major here.
 #pragma once
-#include "ba_handle.h"
+#include "ba_flatten.h"
+#include "ba_kernels.h"
+#include "dev_buf.h"
 #include "dual.h"
 
 namespace ssfm {

@@ -18,7 +18,9 @@
 #include <cstring>
 #include <numeric>
 #include <random>
-#include "ba_handle.h"
+#include "ba_flatten.h"
+#include "ba_kernels.h"
+#include "dev_buf.h"
 
 namespace ssfm {
 

@@ -17,7 +17,9 @@
 // calls on the same input return the same bits.
 #include <algorithm>
 #include <cstring>
-#include "ba_handle.h"
+#include "ba_flatten.h"
+#include "ba_kernels.h"
+#include "dev_buf.h"
 #include "rot_l1_host.h"
 
 namespace ssfm {

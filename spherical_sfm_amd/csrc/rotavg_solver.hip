@@ -8,10 +8,10 @@
 // Ceres defaults apply there (50 iterations, 5 invalid steps, SoftLOneLoss(0.03), first rotation constant, residual scaled
 // by 1/max|log R_rel|).  One lane per edge evaluates the residual with dual numbers (dual.h) and scatters the 3x3 blocks
 // of J^T J into a block-CSR system over the nodes; the normal equations are then solved by the same banded-Cholesky /
-// PCG-refinement path as the BA reduced camera system (ba_handle.h, DC = 3, the shared focal multiplier as border row).
+// PCG-refinement path as the BA reduced camera system (reduced_solve.h, DC = 3, the shared focal multiplier as border row).
 #include <algorithm>
 #include <cstdio>
-#include "ba_handle.h"
+#include "reduced_solve.h"
 #include "dual.h"
 #include "line_search.h"
 

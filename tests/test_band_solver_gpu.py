@@ -21,11 +21,12 @@ def test_band_solver_matches_dense_solve(gpu_ctx, monkeypatch, dc, b, rows, P):
     assert np.abs(X - xr).max() <= 1e-12 * np.abs(xr).max()
 
 
-@pytest.mark.parametrize("b,rows", [(21, [70, 95]), (22, [60, 23, 101]), (26, [120]), (26, [27, 26, 9]), (30, [64, 31, 150])])
+@pytest.mark.parametrize("b,rows", [(21, [70, 95]), (22, [60, 23, 101]), (26, [120]), (26, [27, 26, 9]), (30, [64, 31, 150]), (27, [60, 28])])
 @pytest.mark.parametrize("packed", ["1", "0"])
 def test_wide_band_packed_window_matches_dense_solve(gpu_ctx, monkeypatch, b, rows, packed):
     """Half-widths beyond the square LDS window ring (6x6 blocks, 21..30): the packed-window factorisation of round 4 (band_kernels2p.h) + the back substitution with
-    three task sets per lane, components longer and shorter than the window; SSFM_BAND_PACKED=0: the global-memory kernels they replace."""
+    three task sets per lane, components longer and shorter than the window; SSFM_BAND_PACKED=0: the global-memory kernels they replace.  21, 22, 26 take the
+    6x6-tile kernel, 27 is the one half-width of k_band_chol_v2p<2, 3, 1, 8>, 30 takes <2, 3, 2, 9> (csrc/band_path.h)."""
     from spherical_sfm_amd import ba
     monkeypatch.setenv("SSFM_BAND_PACKED", packed)
     monkeypatch.setenv("SSFM_BAND_SEGMENTS", "1")
