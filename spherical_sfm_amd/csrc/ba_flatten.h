@@ -29,6 +29,7 @@
 #include "../../include/ssfm.h"
 #include "ring_comp.h"
 #include "knobs.h"
+#include "gram_path.h"
 
 namespace ssfm {
 
@@ -103,7 +104,7 @@ struct BAFlat {
     // Signature groups (round 3, k_schur_gram / k_gram_backsub): runs of >= GRAM_MIN_RUN consecutive points observed by exactly the same K cameras,
     // GRAM_KMIN <= K <= GRAM_KMAX (3..8).  Their Schur blocks (off-diagonal and diagonal) and camera-side sums are formed as ONE Gram product per wave task on the
     // matrix cores, each observation linearised once, instead of lane-per-pair from the pair lists and k_cam_sums2 (which then skip these points: pt_grouped).
-    // Tasks are sorted by K (k_schur_gram is launched once per number of 16-row tiles in use).  One record of GRAM_REC ints per task:
+    // Tasks are sorted by K (k_schur_gram is launched once per tile class; the constants and the class rule: gram_path.h).  One record of GRAM_REC ints per task:
     //   [0] first point  [1] points (<= the task length chosen below)  [2] K  [3] first observation (the K of every point follow each other)
     //   [4..11] the cameras, ascending  [12..39] slot[a (a - 1) / 2 + b] (a > b) = block index of (camera a, camera b) in S, bit 30 set when
     //   the stored block is (b, a), i.e. the transpose  [40..47] the diagonal block of every camera
@@ -123,7 +124,6 @@ struct BAFlat {
 inline int gram_part_blocks(int K) { return K * (K + 1) / 2; }
 inline int gram_part_len(int K, int DC) { return gram_part_blocks(K) * DC * DC + K * 5 * DC; }
 constexpr int GRAM_FOLD_PTRS = 31, GRAM_FOLD_HEAD = 32, GRAM_FOLD_SRCS = 128, GRAM_FOLD_STRIDE = GRAM_FOLD_HEAD + GRAM_FOLD_SRCS;      // the fold table of one camera row: <= 29 blocks + the vectors, <= 128 sources
-constexpr int GRAM_KMAX = 8, GRAM_NPAIR = 28, GRAM_REC = 48, GRAM_MIN_RUN = 32, GRAM_KMIN = 3, GRAM_SUB_PTS = 8;      // GRAM_SUB_PTS = GRAM_SUB of ba_kernels.h (points per sub-chunk)
 
 // fork-join over [0, n) in T contiguous chunks; f(thread index, begin, end).  The planner's loops over cameras / points are independent
 // once the prefix sums are known.  The T - 1 helpers are persistent (a pool parked on a condition variable): spawning seven std::threads per
@@ -906,15 +906,14 @@ inline void ba_flatten(const ssfm_ba_problem& P, int nranks, int rank, BAFlat& F
             // max(20, 34.5e-6 observations).  The groups are kept when their estimate (+ the pair path for what stays loose) is below the pair path for everything.
             // SSFM_GRAM_MODEL=0 keeps every group that qualifies.
             if (!(std::getenv("SSFM_GRAM_MODEL") && std::atoi(std::getenv("SSFM_GRAM_MODEL")) == 0) && !runs.empty()) {
-                double cls_pts[4 * 2 * 8] = {0}; double all_pairs = 0, loose_pairs = 0;
+                double cls_pts[GRAM_CLASSES] = {0}; double all_pairs = 0, loose_pairs = 0;
                 { std::vector<double> part(NT, 0.0);
                   parallel_chunks(F.nP, NT, [&](int t, int64_t q0, int64_t q1) { double a = 0; for (int64_t q = q0; q < q1; q++) { const double k = F.pt_start[q + 1] - F.pt_start[q]; a += 0.5 * k * (k - 1); } part[t] += a; });
                   for (double v : part) all_pairs += v; }
                 double grouped_pairs = 0;
                 for (size_t r = 0; r < runs.size(); r += 2) {
-                    const int K = F.pt_start[runs[r] + 1] - F.pt_start[runs[r]], rows = F.DC * K, nt_full = rows / 16, tail = rows - 16 * nt_full;
-                    const int cls = (tail > 0 && tail <= 4 && nt_full >= 1) ? 8 + nt_full : (rows + 15) / 16;      // tile class = launch (ba_solver.hip)
-                    cls_pts[cls] += (double)(runs[r + 1] - runs[r]) * K / 6.0;
+                    const int K = F.pt_start[runs[r] + 1] - F.pt_start[runs[r]];
+                    cls_pts[gram_tile_class(F.DC, K, true)] += (double)(runs[r + 1] - runs[r]) * K / 6.0;      // the class the launch gives it (gram_path.h), the tail classes on as shipped
                     grouped_pairs += 0.5 * K * (K - 1) * (runs[r + 1] - runs[r]);
                 }
                 loose_pairs = all_pairs - grouped_pairs;
@@ -940,7 +939,7 @@ inline void ba_flatten(const ssfm_ba_problem& P, int nranks, int rank, BAFlat& F
                 // round 4: a small problem runs fastest with at most ONE TASK per SIMD -- the shortest task length (64..192) that leaves at most 4 x CUs tasks, runs cut
                 // in equal parts.  Config 2 (300 runs of 333 points): 3 x 112 = 900 tasks 43.9 us; 6 x 56 = 1800 tasks (two waves on three of four SIMDs) 48.2; the
                 // 5 x 64 + 13 of round 3 46.1; 2 x 168 = 600 tasks 49.6 (scripts/prof_gram_ld.py with SSFM_GRAM_PTS, profiles/r04_notes.md).  Round 11: not one WAVE --
-                // two waves that SHARE a task (head and emission paid once: ba_kernels.h k_schur_gram_split, ba_solver.hip LmRun::gram_split) beat the single one,
+                // two waves that SHARE a task (head and emission paid once: ba_kernels.h k_schur_gram_split, gram_path.h: the waves per task of a launch) beat the single one,
                 // 46.5 -> 42.5 us at 3 x 112; the cut itself stays: 2 x 168 with two / three waves per task 51.8 / 58.6 us (profiles/r11_notes.md)
                 for (int g = 64; g <= 192; g += 8) {
                     int64_t tasks = 0; for (size_t r = 0; r < runs.size(); r += 2) tasks += (runs[r + 1] - runs[r] + g - 1) / g;

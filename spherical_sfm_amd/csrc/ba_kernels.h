@@ -19,7 +19,7 @@
 #include <hip/hip_runtime.h>
 #include "ssfm_math.h"
 #include "det_acc.h"
-#include "gram_share.h"
+#include "gram_path.h"
 
 namespace ssfm {
 
@@ -725,12 +725,7 @@ k_schur_pairs2(const double* __restrict__ cam, const double* __restrict__ rot, c
 // History (profiles/r03_notes.md): 32-point sub-chunks on half the lanes 70.7 us at config 2; 16 points on all lanes 57; + prefetch, no zeroing 39.5;
 // emission from LDS instead of per-entry global index loads 35.3; 8-point sub-chunks (12 instead of 7 waves per CU) 380 -> 355 us at the configs[4] size;
 // with the camera-side sums (k_cam_sums2 no longer runs for these cameras) 48.7 us / 400 us against 39.5 + 20.5 / 931 + 414 for the pair path.
-#ifndef SSFM_GRAM_LD
-#define SSFM_GRAM_LD 28      // row stride of the half products in LDS, doubles (swept in round 4: scripts/gpu_gram_ld.sh, profiles/r04_notes.md)
-#endif
-constexpr int GRAM_CAMREC = 34, GRAM_LD = SSFM_GRAM_LD, GRAM_SUB = GRAM_SUB_PTS, GRAM_TAIL = GRAM_KMAX * GRAM_CAMREC + 48 + GRAM_NPAIR / 2 + GRAM_KMAX / 2;
-constexpr int GRAM_VEC = 4 * 6 * GRAM_KMAX;      // split task: behind a wave's slice, its cameras' vectors [K][diag U | Jc^T r | coupling term | S_fc][DC]
-static_assert(GRAM_SUB == GRAM_SHARE_SUB, "gram_share.h deals sub-chunks of GRAM_SUB points");
+// The constants of a task, the tile classes, the LDS slice of a wave (GRAM_LD, GRAM_TAIL, GRAM_VEC, gram_slice) and the launches: gram_path.h.
 // transposing reduction over the 8 lanes that differ in lane bits 0..2: N values per lane in, ceil(N / 8) out; out[j] of a lane is the 8-lane sum of
 // value 8 j + 4 (lane & 1) + 2 ((lane >> 1) & 1) + ((lane >> 2) & 1)
 template <int N, int MASK>
@@ -809,7 +804,7 @@ __device__ __forceinline__ void chol3_scaled(const double* V, double* L) {
 // LF_out: 6 doubles per point, chol3_scaled of the record's V^-1 -- the prologue factors once per point what the unfused loop factors on every observation lane of every sub-chunk
 struct GramFuse { const double* scale_pt; double radius, min_diag, max_diag; double* PS_out; double* gp_out; double* scal; const double* spec; int emit_skip = 0; double* LF_out = nullptr; };
 // one wave task of k_schur_gram / k_schur_gram_any (below): the task's tile shape (NT, TI) is a template parameter, the task index an argument
-// SPLIT (round 11): the W = blockDim.x / 64 waves of the workgroup SHARE the task -- wave w walks the sub-chunks [s_begin, s_end) of gram_share.h through the
+// SPLIT (round 11): the W = blockDim.x / 64 waves of the workgroup SHARE the task -- wave w walks the sub-chunks [s_begin, s_end) of gram_share (gram_path.h) through the
 // prologue and the loop in its own LDS slice, talking to nobody; head (per wave, overlapped) and emission are paid once per task: every wave leaves its tiles, its
 // Jc^T Jc and its cameras' vectors in its slice, ONE workgroup barrier, then the blocks (dealt round-robin over the waves) and the vectors leave as the sum of the
 // W slices in slice order -- as many atomics per task as one wave issues (fewer: Jc^T r goes to rhs together with the coupling term).  A small problem (config 2:
@@ -826,18 +821,19 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
     constexpr int NU = DC * (DC + 1) / 2, NS = NU + 3 * DC, NO = (NS + 7) / 8;          // camera-side sums: [Jc^T Jc (upper) | Jc^T r | -Jc^T Jp V^-1 g | Jc^T (J_f - Jp V^-1 w_f)]
     typedef double v4d_ __attribute__((ext_vector_type(4)));
     const long long t_0 = dbg ? wall_clock64() : 0;
-    extern __shared__ __attribute__((aligned(16))) double sY[];          // per wave: [rows_alloc][GRAM_LD] | camera records [GRAM_KMAX][GRAM_CAMREC] | scales | slots | diagonal slots
+    extern __shared__ __attribute__((aligned(16))) double sY[];          // a slice per wave (gram_path.h: gram_slice): [rows_alloc][GRAM_LD] | camera records | scales | slots | diagonal slots | SPLIT: vectors
     const int lane = threadIdx.x & 63;
-    const int slice_len = rows_alloc * GRAM_LD + GRAM_TAIL + (SPLIT ? GRAM_VEC : 0);
+    const GramSlice lay = gram_slice(rows_alloc, SPLIT);
+    const int slice_len = gram_slice_doubles(rows_alloc, SPLIT);
     double* sYw = sY + (size_t)(threadIdx.x >> 6) * slice_len;
-    double* sCam = sYw + rows_alloc * GRAM_LD;
-    double* sScale = sCam + GRAM_KMAX * GRAM_CAMREC;                     // [DC K] Jacobi scale of Gram row DC k + d
-    int* sSlot = (int*)(sScale + 48);                                    // [GRAM_NPAIR] pair slots, then [GRAM_KMAX] diagonal blocks
-    int* sDiag = sSlot + GRAM_NPAIR;
+    double* sCam = sYw + lay.cam;                                        // [GRAM_KMAX][GRAM_CAMREC]
+    double* sScale = sYw + lay.scale;                                    // [DC K] Jacobi scale of Gram row DC k + d
+    int* sSlot = (int*)(sYw + lay.slot);                                 // [GRAM_NPAIR] pair slots, then [GRAM_KMAX] diagonal blocks
+    int* sDiag = sSlot + lay.diag;
     const int* rec = gr_rec + (size_t)task * GRAM_REC;                   // one record per task (ba_flatten.h): wave-uniform, scalar loads
     const int p0 = __builtin_amdgcn_readfirstlane(rec[0]), cnt = __builtin_amdgcn_readfirstlane(rec[1]), K = __builtin_amdgcn_readfirstlane(rec[2]);
     const int j00 = __builtin_amdgcn_readfirstlane(rec[3]);
-    int s_begin = 0, s_end = cnt;                                        // this wave's share of the task's points (SPLIT: whole sub-chunks, gram_share.h)
+    int s_begin = 0, s_end = cnt;                                        // this wave's share of the task's points (SPLIT: whole sub-chunks, gram_path.h: gram_share)
     if constexpr (SPLIT) {
         gram_share(cnt, (int)(blockDim.x >> 6), __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), s_begin, s_end);
         s_begin = __builtin_amdgcn_readfirstlane(s_begin); s_end = __builtin_amdgcn_readfirstlane(s_end);
@@ -938,7 +934,7 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
 #pragma unroll
     for (int i = 0; i < NS; i++) sm[i] = 0.0;
     const int li = lane & 15, lk = lane >> 4;                          // fragment / accumulator coordinates of the tiles
-    const int lp = lane & (GRAM_SUB - 1), lq = lane >> 3;               // linearisation: point of the sub-chunk, observation (= camera of the group) of this lane
+    const int lp = lane & (GRAM_SUB_PTS - 1), lq = lane >> 3;               // linearisation: point of the sub-chunk, observation (= camera of the group) of this lane
     const int kq = min(lq, K - 1);                                      // clamped: a lane whose camera does not exist repeats the last one, stores nothing and sums nothing
     // point record of a sub-chunk: X, the scaled V^-1 (6) with V^-1 g (3) and V^-1 w_f (3), this lane's observation
     double X[3], V[12]; double2 ob;
@@ -953,7 +949,7 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
     } while (0)
     GRAM_LOAD(s_begin);
     long long t_1 = 0, t_2 = 0;
-    for (int s0 = s_begin; s0 < s_end; s0 += GRAM_SUB) {
+    for (int s0 = s_begin; s0 < s_end; s0 += GRAM_SUB_PTS) {
         wave_lds_handover();                                             // the tiles of the previous sub-chunk have read sY (first pass: sCam is written)
         {
             const bool valid = s0 + lp < cnt;
@@ -1015,13 +1011,13 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
             }
         }
         if (dbg && s0 == 0) t_1 = wall_clock64();                       // first sub-chunk linearised
-        if (s0 + GRAM_SUB < s_end) GRAM_LOAD(s0 + GRAM_SUB);              // in flight while the tiles run
+        if (s0 + GRAM_SUB_PTS < s_end) GRAM_LOAD(s0 + GRAM_SUB_PTS);              // in flight while the tiles run
         wave_lds_handover();
         // tiles of the lower triangle: G(ti, tj) += Y(ti rows) Y(tj rows)^T over the 24 columns of this sub-chunk, 4 per instruction
         // (only the row tiles that hold cameras: the tasks are sorted by K and every tile count has its own launch -- DC K <= 16: one product per k-step,
         // <= 32: three, else six.  Guards in one loop cost the full case 6 %; two or three loop variants in one kernel 35-40 %: the accumulators left their AGPRs)
 #pragma unroll
-        for (int st = 0; st < 3 * GRAM_SUB / 4; st++) {
+        for (int st = 0; st < 3 * GRAM_SUB_PTS / 4; st++) {
             double fr[NT];
 #pragma unroll
             for (int t = 0; t < NT; t++) fr[t] = sYw[(size_t)min(16 * t + li, rows_alloc - 1) * GRAM_LD + 4 * st + lk];
@@ -1032,9 +1028,9 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
                 for (int tj = 0; tj <= ti; tj++) { acc[tix] = __builtin_amdgcn_mfma_f64_16x16x4f64(fr[ti], fr[tj], acc[tix], 0, 0, 0); tix++; }
         }
         if constexpr (TI > 0) {
-            double a4[3 * GRAM_SUB / 4], b4[TI][3 * GRAM_SUB / 4];
+            double a4[3 * GRAM_SUB_PTS / 4], b4[TI][3 * GRAM_SUB_PTS / 4];
 #pragma unroll
-            for (int st = 0; st < 3 * GRAM_SUB / 4; st++) {
+            for (int st = 0; st < 3 * GRAM_SUB_PTS / 4; st++) {
                 a4[st] = sYw[(size_t)min(16 * NT + (lane & 3), rows_alloc - 1) * GRAM_LD + 4 * st + lk];
 #pragma unroll
                 for (int u = 0; u < TI; u++) {
@@ -1043,7 +1039,7 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
                 }
             }
 #pragma unroll
-            for (int st = 0; st < 3 * GRAM_SUB / 4; st++)
+            for (int st = 0; st < 3 * GRAM_SUB_PTS / 4; st++)
 #pragma unroll
                 for (int u = 0; u < TI; u++) tacc[u] = __builtin_amdgcn_mfma_f64_4x4x4f64(a4[st], b4[u][st], tacc[u], 0, 0, 0);
         }
@@ -1057,8 +1053,8 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
     // has 16 (t + 1) + 1 columns; a store is lane coordinates + a constant), Jc^T Jc of every camera is added to its diagonal block there, and the K (K + 1) / 2 blocks
     // leave in block order: entry e of block (a, b) is G[6 a + e / DC][6 b + e % DC] -- consecutive lanes, consecutive addresses of S.
     wave_lds_handover();
-    double* sG = sYw;                                                    // over sY and the camera records (both done): gram_g_off(DC K) <= rows_alloc GRAM_LD + GRAM_KMAX GRAM_CAMREC
-    auto g_off = [](int R) { const int t = R >> 4; return 128 * t * t + 144 * t + (R & 15) * (16 * t + 17); };
+    double* sG = sYw;                                                    // over sY and the camera records (both done), in front of the scales (gram_path.h: gram_overlay_fits)
+    auto g_off = [](int R) { return gram_g_off(R); };                    // (row R of G; through a lambda the kernels compile to the instructions they had with the formula in place)
     {
         double cs[NT], rs[NT][4];
 #pragma unroll
@@ -1099,7 +1095,7 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
             const int c = cam_k;
             const double* sc = sScale + DC * lq;
             const int i0 = 4 * (lane & 1) + 2 * ((lane >> 1) & 1) + ((lane >> 2) & 1);
-            double* vec = sYw + rows_alloc * GRAM_LD + GRAM_TAIL + lq * 4 * DC;      // (SPLIT: this wave's vectors of camera lq, summed over the slices behind the barrier)
+            double* vec = sYw + lay.vec + lq * 4 * DC;      // (SPLIT: this wave's vectors of camera lq, summed over the slices behind the barrier)
 #pragma unroll
             for (int j = 0; j < NO; j++) {
                 const int i = 8 * j + i0;
@@ -1137,11 +1133,11 @@ schur_gram_task(const double* __restrict__ cam, const double* __restrict__ rot, 
             const int k = idx / (4 * DC), r = idx - k * 4 * DC, which = r / DC, a = r - which * DC;
             if (which == 3 && !focal_free) continue;
             const int c = rec[4 + k];
-            const double v = over_slices(rows_alloc * GRAM_LD + GRAM_TAIL + idx);
+            const double v = over_slices(lay.vec + idx);
             if (which == 0) zadd(dz, &Udiag[c * DC + a], v);
             else if (which == 1) {                                       // Jc^T r: the raw gradient, and into rhs together with the coupling term
                 zadd(dz, &gcraw[c * DC + a], v);
-                zadd(dz, &rhs[c * DC + a], v + over_slices(rows_alloc * GRAM_LD + GRAM_TAIL + idx + DC));
+                zadd(dz, &rhs[c * DC + a], v + over_slices(lay.vec + idx + DC));
             } else if (which == 3) zadd(dz, &Sfc[c * DC + a], v);
         }
         if constexpr (2 * BB > 64) {                                     // a block per instruction (see below), the blocks dealt round-robin over the waves
@@ -1226,7 +1222,7 @@ k_schur_gram(const double* __restrict__ cam, const double* __restrict__ rot, con
     schur_gram_task<DC, NT, TI, FUSE>(cam, rot, pts, focal, obs_xy, gr_rec, scale_cam, scale_f, PS, loss, la, rows_alloc, focal_free, task, S_val, rhs, Udiag, Sfc, gcraw, dbg, fz, dz);
 }
 // Round 11: ONE task per workgroup, shared by its blockDim.x / 64 = 2 .. 4 waves (schur_gram_task: SPLIT) -- the launch of a problem with fewer tasks than the chip
-// holds waves of this kernel (ba_solver.hip: LmRun::gram_split).  Same arguments, same tile classes; dynamic LDS = a slice + GRAM_VEC doubles per wave.
+// holds waves of this kernel (gram_path.h: the waves per task of a launch).  Same arguments, same tile classes; dynamic LDS = a slice + GRAM_VEC doubles per wave.
 template <int DC, int NT, int TI = 0, bool FUSE = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
 k_schur_gram_split(const double* __restrict__ cam, const double* __restrict__ rot, const double* __restrict__ pts, const double* __restrict__ focal,
@@ -1253,6 +1249,8 @@ k_schur_gram_any(const double* __restrict__ cam, const double* __restrict__ rot,
     const int rows = DC * __builtin_amdgcn_readfirstlane(gr_rec[(size_t)task * GRAM_REC + 2]);
     const GramFuse fz{};
 #define SSFM_GRAM_ANY(NT_, TI_) schur_gram_task<DC, NT_, TI_, false>(cam, rot, pts, focal, obs_xy, gr_rec, scale_cam, scale_f, PS, loss, la, rows_alloc, focal_free, task, S_val, rhs, Udiag, Sfc, gcraw, nullptr, fz, dz)
+    // gram_tile_class (gram_path.h), spelled out on rows: through the function, as a switch or as a cascade on the class, the 6-dof kernel compiles to other
+    // registers and scratch (83 SGPRs / 44 B against 82 / 52 B) -- kept byte for byte until that is measured; tests/native/gram_path_check.cpp holds the two together
     if (rows <= 16) SSFM_GRAM_ANY(1, 0);
     else if (rows <= 20 && use_t4) SSFM_GRAM_ANY(1, 2);
     else if (rows <= 32) SSFM_GRAM_ANY(2, 0);
@@ -2146,7 +2144,7 @@ k_point_backsub(const double* __restrict__ cam, const double* __restrict__ rot, 
 // steps sit in LDS, every lane linearises ONE observation, what the point's step needs is folded over the 8 observation lanes of the point, every lane of the
 // point then knows the step and evaluates ITS observation at the candidate.  No dependent index load anywhere (the observations of a group are consecutive,
 // K per point); the next sub-chunk's records are in flight during the arithmetic.
-constexpr int GBS_CAMC = 12, GBS_TAIL = GRAM_KMAX * (GRAM_CAMREC + GBS_CAMC + 6), GBS_WAVES = 4;
+// (GBS_CAMC, GBS_TAIL, GBS_WAVES, GBS2_PT, GBS2_STAGE, GBS2_TAIL and the launch's byte count: gram_path.h)
 // ---- round 6: the point records staged through LDS and the 8 observation lanes of a point ADJACENT -------------------------------------
 // k_gram_backsub kept two copies of a sub-chunk's point records in registers (the one in use and the one in flight: 2 x 17 doubles per lane, every value
 // requested by the eight lanes of its point -- sixteen load instructions per sub-chunk) and folds B^T a over lanes 8 / 16 / 32 apart with ds_bpermute (three dependent
@@ -2156,7 +2154,6 @@ constexpr int GBS_CAMC = 12, GBS_TAIL = GRAM_KMAX * (GRAM_CAMREC + GBS_CAMC + 6)
 // The point's step comes from the record PS alone: with w = sum over its observations of Jp^T m (m = the camera / focal part of the model residual) the step in the
 // caller's coordinates is  u = PS[6..8] - PS[0..5] w   (PS[0..5] = S V^-1 S, PS[6..8] = S V^-1 g, S = the Jacobi scales: k_point_lin) -- no g_p, no scales, no
 // reciprocal; a fixed point has an all-zero record.  Sums in another order than k_gram_backsub's (tests: oracle tolerance).
-constexpr int GBS2_PT = 18, GBS2_STAGE = 2 * GRAM_SUB * GBS2_PT, GBS2_TAIL = GBS_TAIL + GBS2_STAGE;
 template <int CTRL> __device__ __forceinline__ double dpp_f64(double v) {
     const long long b = __double_as_longlong(v);
     const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), CTRL, 0xf, 0xf, false);
@@ -2194,8 +2191,8 @@ k_gram_backsub2(const double* __restrict__ cam, const double* __restrict__ rot, 
     const int* rec = gr_rec + (size_t)task * GRAM_REC;
     const int p0 = __builtin_amdgcn_readfirstlane(rec[0]), cnt = __builtin_amdgcn_readfirstlane(rec[1]), K = __builtin_amdgcn_readfirstlane(rec[2]);
     const int j00 = __builtin_amdgcn_readfirstlane(rec[3]);
-    const int sub_per = ((cnt + GRAM_SUB - 1) / GRAM_SUB + split - 1) / split;
-    const int s_begin = part * sub_per * GRAM_SUB, s_end = min(cnt, s_begin + sub_per * GRAM_SUB);
+    const int sub_per = ((cnt + GRAM_SUB_PTS - 1) / GRAM_SUB_PTS + split - 1) / split;
+    const int s_begin = part * sub_per * GRAM_SUB_PTS, s_end = min(cnt, s_begin + sub_per * GRAM_SUB_PTS);
     if (s_begin >= cnt) return;
     const int camv = rec[4 + (lane & (GRAM_KMAX - 1))];                 // the task's cameras as a lane vector (gram_cam_of)
     gram_gather<33, GRAM_CAMREC, 6>(cam, rot, camv, K, lane, sCam);
@@ -2214,7 +2211,7 @@ k_gram_backsub2(const double* __restrict__ cam, const double* __restrict__ rot, 
         for (int i = 0; i < 3; i++) sStep[6 * lane + 3 + i] = Mm[3 * i] * dr[0] + Mm[3 * i + 1] * dr[1] + Mm[3 * i + 2] * dr[2];
     }
     const double f = focal[0], sf = scale_f[0], yf = y[Nc * DC], fcand = focal_c[0];
-    const int lq = lane & (GRAM_SUB - 1), lp = lane >> 3;               // observation (= camera of the group), point of the sub-chunk
+    const int lq = lane & (GRAM_SUB_PTS - 1), lp = lane >> 3;               // observation (= camera of the group), point of the sub-chunk
     const int kq = min(lq, K - 1);
     double acc[4] = {0, 0, 0, 0};   // model, step2, xn2, candidate cost
     CostAcc cost(la);               // (one factor per sub-chunk of this lane: the split decides which)
@@ -2230,7 +2227,7 @@ k_gram_backsub2(const double* __restrict__ cam, const double* __restrict__ rot, 
     } while (0)
 #define GBS2_STAGE_STORE(buf_)                                                                                                    \
     do {                                                                                                                          \
-        double* d_ = sPt + (buf_) * GRAM_SUB * GBS2_PT;                                                                           \
+        double* d_ = sPt + (buf_) * GRAM_SUB_PTS * GBS2_PT;                                                                           \
         if (lane < 24) d_[a_dst] = ra;                                                                                            \
         d_[b_dst] = rb;                                                                                                           \
         if (lane < 32) d_[c_dst] = rc;                                                                                            \
@@ -2238,20 +2235,20 @@ k_gram_backsub2(const double* __restrict__ cam, const double* __restrict__ rot, 
     GBS2_LOAD(s_begin);
     ob = obs_xy[j00 + (size_t)min(s_begin + lp, cnt - 1) * K + kq];
     GBS2_STAGE_STORE(0);
-    if (s_begin + GRAM_SUB < s_end) GBS2_LOAD(s_begin + GRAM_SUB);
+    if (s_begin + GRAM_SUB_PTS < s_end) GBS2_LOAD(s_begin + GRAM_SUB_PTS);
     wave_lds_handover();
     int buf = 0;
-    for (int s0 = s_begin; s0 < s_end; s0 += GRAM_SUB, buf ^= 1) {
+    for (int s0 = s_begin; s0 < s_end; s0 += GRAM_SUB_PTS, buf ^= 1) {
         const bool valid = s0 + lp < cnt, act = valid && lq < K;
         const double2 on = ob;
         const size_t pn = (size_t)(p0 + min(s0 + lp, cnt - 1));
         // the next sub-chunk's records (loaded one iteration ago) go to the other buffer -- its readers finished before the previous hand-over --, the one after that is requested
-        if (s0 + GRAM_SUB < s_end) {
+        if (s0 + GRAM_SUB_PTS < s_end) {
             GBS2_STAGE_STORE(buf ^ 1);
-            ob = obs_xy[j00 + (size_t)min(s0 + GRAM_SUB + lp, cnt - 1) * K + kq];
-            if (s0 + 2 * GRAM_SUB < s_end) GBS2_LOAD(s0 + 2 * GRAM_SUB);
+            ob = obs_xy[j00 + (size_t)min(s0 + GRAM_SUB_PTS + lp, cnt - 1) * K + kq];
+            if (s0 + 2 * GRAM_SUB_PTS < s_end) GBS2_LOAD(s0 + 2 * GRAM_SUB_PTS);
         }
-        const double* pr = sPt + (buf * GRAM_SUB + lp) * GBS2_PT;
+        const double* pr = sPt + (buf * GRAM_SUB_PTS + lp) * GBS2_PT;
         const double Xn[3] = {pr[0], pr[1], pr[2]};
         double m0 = 0.0, m1 = 0.0, r0 = 0.0, r1 = 0.0, J0[3] = {0, 0, 0}, J1[3] = {0, 0, 0}, w[3] = {0, 0, 0};
         if (act) {

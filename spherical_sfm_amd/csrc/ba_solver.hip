@@ -56,8 +56,8 @@ struct LmRun {
     // host's critical path between two iterations: only with profiling on (ssfm_ba_set_profiling) or options.verbose
     const bool phases;
     // the knobs of a solve (read_knobs)
-    bool poll = false, spec_on = false, fuse_lin = false; int gram_bs = -1, gbs_split_env = 0;
-    int gram_split[5] = {1, 1, 1, 1, 1};                                 // waves per task of k_schur_gram, per tile class (read_knobs)
+    bool poll = false, spec_on = false;
+    GramPath gp;                                                     // the Gram launches of the assembly and the grouped back substitution (gram_path.h)
     double *host_scal = nullptr, *host_pcg1 = nullptr;               // the iteration's scalars and solver flags as the host reads them
     // trust region
     double radius, decrease_factor = 2.0, x_norm = 0.0, x_cost = 0.0, minimum_cost = std::numeric_limits<double>::max();
@@ -151,35 +151,19 @@ struct LmRun {
         // launches the rest.  The host's own decision stays authoritative: a speculative launch that should not have run only touched
         // scratch arrays and the next zone, which is then cleared again.  SSFM_LM_SPECULATE=0 turns it off.
         spec_on = poll && nP > 0 && knob_env_int("SSFM_LM_SPECULATE", 1) != 0;
-        gram_bs = knob_env_int("SSFM_GRAM_BACKSUB", -1);             // 0 / 1 forces k_gram_backsub2 off / on (back_substitute)
-        gbs_split_env = knob_env_int("SSFM_GBS_SPLIT", 0);           // > 0: waves per task of k_gram_backsub2
-        // Every point in a signature group, one Gram launch per tile class and nothing else in the assembly: the Gram task does the point pass of its own points in a
-        // prologue (ba_kernels.h: FUSE) and k_point_lin does not run; the speculative launch behind k_publish is then the Gram kernel of the NEXT iteration, accumulating
-        // into the next zone.  Not with pair or camera-sum tasks (they read PS of points other tasks own), not in the mixed-class k_schur_gram_any launch, not with
-        // SSFM_DETERMINISTIC=1 (the fused epilogue adds its sums with plain atomics).  SSFM_GRAM_FUSE=0: k_point_lin + the unfused kernel (profiles/r09_notes.md).
-        { int cls_end[5]; const int n_cls = gram_classes(cls_end);
-          fuse_lin = knob_env_int("SSFM_GRAM_FUSE", 1) != 0 && !h->det && nP > 0 && !F.gr_rec.empty() && F.gram_points == (int64_t)nP && F.chunk_cam.empty() && F.cs_task_cam.empty()
-                     && !(F.gram_any && n_cls > 1) && cls_end[4] == cls_end[3];      // (no task of the three-tile class: gram_kernel_of)
-          // Waves per task of k_schur_gram (ba_kernels.h: SPLIT).  A wave of it takes half a SIMD's registers, so the chip holds 8 waves per CU: a launch with fewer
-          // tasks than that gives every task W of them, W <= 4 and at most one per sub-chunk of the launch's longest task (config 2: 900 tasks -> 2; <= 512 -> 4;
-          // the configs[4] size, thousands of tasks -> 1 = the unsplit kernel).  SSFM_GRAM_SPLIT=1..4 forces W.  SSFM_DETERMINISTIC=1 keeps W = 1 whatever the knob
-          // says: its per-task partial buffer takes plain stores of ONE wave per task (det_acc.h), and the limbs' order independence is tested on the unsplit kernel.
-          const int split_env = knob_env_int("SSFM_GRAM_SPLIT", 0);
-          const bool unsplit = h->det || SSFM_LAB_KNOB("SSFM_GRAM_WAVES", 1) != 1 || SSFM_LAB_KNOB("SSFM_GRAM_EMIT_SKIP", 0) != 0 || SSFM_LAB_KNOB("SSFM_GRAM_STAMPS", 0) != 0
-                               || (F.gram_any && n_cls > 1);             // (the lab shapes and the mixed-class launch k_schur_gram_any stay unsplit)
-          for (int cl = 0; cl < 5; cl++) {
-              const int t0 = cl ? cls_end[cl - 1] : 0, t1 = cls_end[cl];
-              gram_split[cl] = 1;
-              if (t1 <= t0 || unsplit) continue;
-              int max_sub = 1;
-              for (int t = t0; t < t1; t++) max_sub = std::max(max_sub, (F.gr_rec[(size_t)t * GRAM_REC + 1] + GRAM_SUB_PTS - 1) / GRAM_SUB_PTS);
-              // a workgroup lives on ONE CU: 8 / W of them fit there, so 4 waves per task while the tasks fit 2 per CU, 2 while they fit 4 per CU (3 holds no more
-              // workgroups per CU than 4 does: 600 tasks x 3 waves ran in two rounds, 58.6 us against 51.8 with 2 -- profiles/r11_notes.md)
-              const int ntask = t1 - t0, by_count = ntask <= 2 * ctx->num_cus ? 4 : ntask <= 4 * ctx->num_cus ? 2 : 1;
-              gram_split[cl] = (split_env >= 1 && split_env <= 4) ? split_env : std::min(max_sub, by_count);
-              if (std::getenv("SSFM_PLAN_TIMING")) std::fprintf(stderr, "[solve] gram split: class %d, %d tasks, longest %d sub-chunks: %d waves per task\n", cl, t1 - t0, max_sub, gram_split[cl]);
-          }
-        }
+        // the Gram launches and the grouped back substitution: what the plan holds, the device and the knobs in, one GramPath out (gram_path.h states every rule)
+        GramPathIn in; in.DC = DC; in.gr_rec = F.gr_rec.data(); in.ng = (int)(F.gr_rec.size() / GRAM_REC);
+        in.gram_points = F.gram_points; in.gram_obs = F.gram_obs; in.nP = nP; in.M = F.M;
+        in.pair_tasks = !F.chunk_cam.empty(); in.cam_sum_tasks = !F.cs_task_cam.empty(); in.gram_any = F.gram_any; in.det = h->det; in.focal_free = F.focal_free; in.num_cus = ctx->num_cus;
+        in.env_fuse = knob_env_int("SSFM_GRAM_FUSE", 1); in.env_split = knob_env_int("SSFM_GRAM_SPLIT", 0);
+        in.env_backsub = knob_env_int("SSFM_GRAM_BACKSUB", -1); in.env_gbs_split = knob_env_int("SSFM_GBS_SPLIT", 0);
+        GramPathLab lab;      // the shipped library compiles the defaults in
+        lab.gram_waves = SSFM_LAB_KNOB("SSFM_GRAM_WAVES", 1); lab.t4 = SSFM_LAB_KNOB("SSFM_GRAM_T4", 1) != 0; lab.emit_skip = SSFM_LAB_KNOB("SSFM_GRAM_EMIT_SKIP", 0);
+        lab.stamps = SSFM_LAB_KNOB("SSFM_GRAM_STAMPS", 0) != 0; lab.backsub_lpp = SSFM_LAB_KNOB("SSFM_BACKSUB_LPP", 0); lab.publish_fused = fused_publish();
+        gp = gram_path(in, lab);
+        if (std::getenv("SSFM_PLAN_TIMING") && !gp.unsplit)
+            for (int i = 0; i < gp.n_launch; i++) { const GramLaunch& l = gp.launch[i];
+                std::fprintf(stderr, "[solve] gram split: class %d, %d tasks, longest %d sub-chunks: %d waves per task\n", l.cls, l.t1 - l.t0, l.max_sub, l.waves); }
         return SSFM_OK;
     }
 
@@ -262,83 +246,55 @@ struct LmRun {
                fused ? h->pub_ticket.p : (int*)nullptr, fused ? h->host_pub : (double*)nullptr, fused ? ++ctx->pub_seq : 0ull, fused ? *fused : LmGate(), spec,
                fused ? (long long*)nullptr : lacc);
     }
-    // waves per task: a small problem (config 2: 900 tasks on 1024 SIMDs) runs with several waves per SIMD, each with a share of its task's sub-chunks
-    // (config 2, hipEvent: 1 wave per task 26.3 us, 2: 24, 4: 21.1, 6 / 8: 24; k_point_backsub 23.0)
+    // the points of the signature groups: waves per task, workgroups and bytes from the plan (gram_path.h)
     void gram_backsub(bool res) {
-        const int ng = (int)(F.gr_rec.size() / GRAM_REC);
-        const int gbs_wave_target = 14 * ctx->num_cus;      // ~3.5 waves per SIMD in flight (config 2: 900 tasks x 4; 1200 tasks x 1 took 31 us, x 3: see profiles/r06_notes.md r06i)
-        const int gbs_split = gbs_split_env > 0 ? std::min(8, gbs_split_env) : std::max(1, std::min(4, (gbs_wave_target + ng - 1) / std::max(1, ng)));
-        LAUNCH(h, KID_GRAM_BACKSUB, k_gram_backsub2<DC>, (ng * gbs_split + GBS_WAVES - 1) / GBS_WAVES + (res ? 1 : 0), 64 * GBS_WAVES, GBS_WAVES * GBS2_TAIL * sizeof(double), x.cam, x.rot, x.pts, x.focal, oxy, ng, h->gr_rec.p,
+        LAUNCH(h, KID_GRAM_BACKSUB, k_gram_backsub2<DC>, gp.gbs_grid + (res ? 1 : 0), 64 * GBS_WAVES, gp.gbs_lds, x.cam, x.rot, x.pts, x.focal, oxy, (int)(F.gr_rec.size() / GRAM_REC), h->gr_rec.p,
                h->scale_cam.p, h->scale_f.p, h->Vs.p, h->px.p, Nc, loss, la, c.cam, c.rot, c.focal, c.pts, h->scal.p,
-               h->rhs, h->pq.p, h->Sfc, h->Sff.p, O.pcg_tolerance * O.pcg_tolerance, res ? h->pr.p : (double*)nullptr, h->pcg.p, lacc, gbs_split);
+               h->rhs, h->pq.p, h->Sfc, h->Sff.p, O.pcg_tolerance * O.pcg_tolerance, res ? h->pr.p : (double*)nullptr, h->pcg.p, lacc, gp.gbs_split);
     }
-    // the kernel of a tile class (launch_gram)
+    // the kernel of a tile class (gram_path.h: GRAM_CLASS_*), unsplit or with the task shared by the waves of a workgroup.  A class that 3-dof cameras never
+    // reach has no split kernel for them.
     using GramKernel = decltype(&k_schur_gram<DC, 1, 0, false>);
-    template <bool FUSE> static GramKernel gram_kernel_of(int cls) {
-        // (FUSE: the three-tile class has no fused form -- k_schur_gram<6, 3, 0> sits at its 256 registers and the prologue costs it 16 B more scratch; read_knobs keeps
-        //  k_point_lin for a problem with such tasks.  3-dof cameras never reach the classes behind the third.)
-        static const GramKernel k[5] = {k_schur_gram<DC, 1, 0, FUSE>, k_schur_gram<DC, 1, 2, FUSE>, k_schur_gram<DC, 2, 0, FUSE>, k_schur_gram<DC, 2, 3, FUSE && DC == 6>, k_schur_gram<DC, 3, 0, false>};
-        return k[cls];
+    template <bool FUSE, bool SPLIT, int CLS> static GramKernel gram_kernel_at() {
+        constexpr bool exists = DC == 6 || GRAM_CLASS_DC3[CLS];
+        constexpr int NT = GRAM_CLASS_NT[CLS], TI = GRAM_CLASS_TI[CLS];
+        constexpr bool fuse = FUSE && GRAM_CLASS_FUSED[CLS] && exists;
+        if constexpr (!SPLIT) return k_schur_gram<DC, NT, TI, fuse>;
+        else if constexpr (exists) return k_schur_gram_split<DC, NT, TI, fuse>;
+        else return nullptr;
     }
-    // the same classes with the task shared by the waves of a workgroup (3-dof cameras: three classes, launch_gram asks for no other)
-    template <bool FUSE> static GramKernel gram_split_kernel_of(int cls) {
-        static const GramKernel k[5] = {k_schur_gram_split<DC, 1, 0, FUSE>, k_schur_gram_split<DC, 1, 2, FUSE>, k_schur_gram_split<DC, 2, 0, FUSE>,
-                                        DC == 6 ? k_schur_gram_split<6, 2, 3, FUSE> : nullptr, DC == 6 ? k_schur_gram_split<6, 3, 0, false> : nullptr};
+    template <bool FUSE, bool SPLIT> static GramKernel gram_kernel_of(int cls) {
+        static const GramKernel k[GRAM_CLASSES] = {gram_kernel_at<FUSE, SPLIT, 0>(), gram_kernel_at<FUSE, SPLIT, 1>(), gram_kernel_at<FUSE, SPLIT, 2>(), gram_kernel_at<FUSE, SPLIT, 3>(), gram_kernel_at<FUSE, SPLIT, 4>()};
         return k[cls];
     }
     GramKernel gram_kernel(int cls, bool split) const {
-        if (split) return fuse_lin ? gram_split_kernel_of<true>(cls) : gram_split_kernel_of<false>(cls);
-        return fuse_lin ? gram_kernel_of<true>(cls) : gram_kernel_of<false>(cls);
+        if (split) return gp.fuse_lin ? gram_kernel_of<true, true>(cls) : gram_kernel_of<false, true>(cls);
+        return gp.fuse_lin ? gram_kernel_of<true, false>(cls) : gram_kernel_of<false, false>(cls);
     }
-    // one launch per tile class (the tasks are sorted by K, i.e. by rows = DC K): rows <= 16 -> 1 row tile of 16; 17..20 -> 1 tile + a tail of <= 4 rows through
-    // the 4x4x4 instruction; <= 32 -> 2 tiles; 33..36 -> 2 tiles + tail; else 3 tiles.  cls_end[cl] = end of class cl's task range; returns the classes in use
-    static bool gram_t4() { return SSFM_LAB_KNOB("SSFM_GRAM_T4", 1) != 0; }
-    int gram_classes(int (&cls_end)[5]) const {
-        const int ng = (int)(F.gr_rec.size() / GRAM_REC);
-        const bool t4 = gram_t4();
-        auto tile_class = [&](int K) { const int rows = DC * K; return rows <= 16 ? 0 : (rows <= 20 && t4) ? 1 : rows <= 32 ? 2 : (rows <= 36 && t4) ? 3 : 4; };
-        for (int cl = 0; cl < 5; cl++) cls_end[cl] = 0;
-        for (int t = 0; t < ng; t++) { const int c0 = tile_class(F.gr_rec[(size_t)t * GRAM_REC + 2]); for (int cl = c0; cl < 5; cl++) cls_end[cl] = t + 1; }
-        int n_cls = 0; for (int cl = 0; cl < 5; cl++) if (cls_end[cl] > (cl ? cls_end[cl - 1] : 0)) n_cls++;
-        return n_cls;
-    }
-    // signature groups: Gram products on the matrix cores (ba_kernels.h: k_schur_gram); one launch per tile class.  at = the state it linearises at,
+    // signature groups: Gram products on the matrix cores (ba_kernels.h: k_schur_gram), the launches of the plan (gram_path.h).  at = the state it linearises at,
     // z = the zone it accumulates into, spec = device-side [go, radius] of a speculative launch (fused point pass only)
     int launch_gram(const State& at, const ZoneView& z, const double* spec) {
-        const int ng = (int)(F.gr_rec.size() / GRAM_REC);
-        const int gram_waves = std::min(4, std::max(1, SSFM_LAB_KNOB("SSFM_GRAM_WAVES", 1)));   // waves (tasks) per workgroup: 1 measured best (2: +14 %, 4: +13 % at the configs[4] size)
         long long* gram_dbg = nullptr;
 #ifdef SSFM_LAB
-        gram_dbg = lab_gram_stamps_begin(ng);
+        gram_dbg = lab_gram_stamps_begin(gp.any_launch.t1);              // (any_launch spans all tasks: t1 = their count)
 #endif
-        int cls_end[5]; const int n_cls = gram_classes(cls_end);
-        const bool gram_any = F.gram_any;                                 // SSFM_GRAM_ANY as the PLAN read it (one value for the cost model and the launch; 0: one launch per tile class)
-        const bool any_ok = gram_any && n_cls > 1 && gram_waves == 1 && !gram_dbg && !fuse_lin;
-        if (any_ok) {
-            // tracks of mixed length: every tile class in ONE launch (ba_kernels.h: k_schur_gram_any), LDS for the largest class
-            const int rows_alloc = DC * F.gr_rec[(size_t)(ng - 1) * GRAM_REC + 2];
-            const size_t gram_lds = ((size_t)rows_alloc * GRAM_LD + GRAM_TAIL) * sizeof(double);
-            if (gram_lds > 48 * 1024) SSFM_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_schur_gram_any<DC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_lds));
-            LAUNCH(h, KID_SCHUR_GRAM, (k_schur_gram_any<DC>), ng, 64, gram_lds, at.cam, at.rot, at.pts, at.focal, oxy, ng, h->gr_rec.p, h->scale_cam.p, h->scale_f.p, h->Vs.p, loss, la, rows_alloc,
-                   F.focal_free ? 1 : 0, gram_t4() ? 1 : 0, z.S_val, z.rhs, z.Udiag, z.Sfc, z.gcraw, z.det);
+        if (gp.any && !gram_dbg) {                                       // (the stamped launch of the lab library runs per class)
+            const GramLaunch& l = gp.any_launch;
+            if (l.lds > 48 * 1024) SSFM_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_schur_gram_any<DC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
+            LAUNCH(h, KID_SCHUR_GRAM, (k_schur_gram_any<DC>), l.grid, l.block, l.lds, at.cam, at.rot, at.pts, at.focal, oxy, l.t1, h->gr_rec.p, h->scale_cam.p, h->scale_f.p, h->Vs.p, loss, la, l.rows_alloc,
+                   gp.focal_free ? 1 : 0, gp.t4 ? 1 : 0, z.S_val, z.rhs, z.Udiag, z.Sfc, z.gcraw, z.det);
         } else {
-            GramFuse fz; fz.scale_pt = h->scale_pt.p; fz.radius = radius; fz.min_diag = O.min_lm_diagonal; fz.max_diag = O.max_lm_diagonal; fz.PS_out = h->Vs.p; fz.LF_out = h->Lf.p; fz.gp_out = h->gp.p; fz.scal = z.scal; fz.emit_skip = SSFM_LAB_KNOB("SSFM_GRAM_EMIT_SKIP", 0); fz.spec = spec;
-            for (int cl = 0; cl < (DC == 6 ? 5 : 3); cl++) {              // (3-dof cameras: two row tiles at most)
-                const int t0 = cl ? cls_end[cl - 1] : 0, t1 = cls_end[cl];
-                if (t1 <= t0) continue;
-                // W > 1: one task per workgroup, shared by its W waves, a slice of LDS (+ the vectors' stash) each; else gram_waves tasks per workgroup, a wave each
-                const int W = (gram_waves == 1 && !gram_dbg && !fz.emit_skip) ? gram_split[cl] : 1;
-                const GramKernel kernel = gram_kernel(cl, W > 1);
-                const int rows_alloc = DC * F.gr_rec[(size_t)(t1 - 1) * GRAM_REC + 2];              // the largest K of the class: its last task
-                const size_t gram_lds = W > 1 ? (size_t)W * ((size_t)rows_alloc * GRAM_LD + GRAM_TAIL + GRAM_VEC) * sizeof(double)
-                                              : (size_t)gram_waves * ((size_t)rows_alloc * GRAM_LD + GRAM_TAIL) * sizeof(double);
-                if (gram_lds > 48 * 1024) SSFM_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_lds));
-                LAUNCH(h, KID_SCHUR_GRAM, kernel, W > 1 ? t1 - t0 : (t1 - t0 + gram_waves - 1) / gram_waves, W > 1 ? 64 * W : 64 * gram_waves, gram_lds, at.cam, at.rot, at.pts, at.focal, oxy, t1, h->gr_rec.p,
-                       h->scale_cam.p, h->scale_f.p, h->Vs.p, loss, la, rows_alloc, F.focal_free ? 1 : 0, t0, z.S_val, z.rhs, z.Udiag, z.Sfc, z.gcraw, gram_dbg, fz, z.det);
+            GramFuse fz; fz.scale_pt = h->scale_pt.p; fz.radius = radius; fz.min_diag = O.min_lm_diagonal; fz.max_diag = O.max_lm_diagonal; fz.PS_out = h->Vs.p; fz.LF_out = h->Lf.p; fz.gp_out = h->gp.p; fz.scal = z.scal; fz.emit_skip = gp.lab.emit_skip; fz.spec = spec;
+            for (int i = 0; i < gp.n_launch; i++) {
+                const GramLaunch& l = gp.launch[i];
+                const GramKernel kernel = gram_kernel(l.cls, l.split);
+                if (l.lds > 48 * 1024) SSFM_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
+                LAUNCH(h, KID_SCHUR_GRAM, kernel, l.grid, l.block, l.lds, at.cam, at.rot, at.pts, at.focal, oxy, l.t1, h->gr_rec.p,
+                       h->scale_cam.p, h->scale_f.p, h->Vs.p, loss, la, l.rows_alloc, gp.focal_free ? 1 : 0, l.t0, z.S_val, z.rhs, z.Udiag, z.Sfc, z.gcraw, gram_dbg, fz, z.det);
             }
         }
 #ifdef SSFM_LAB
-        if (gram_dbg) lab_gram_stamps_print(gram_dbg, ng);
+        if (gram_dbg) lab_gram_stamps_print(gram_dbg, gp.any_launch.t1);
 #endif
         return SSFM_OK;
     }
@@ -352,7 +308,7 @@ struct LmRun {
         // per-kernel profiling: the first launch after the host's hand-over would carry the queue's wake-up inside its event bracket (k_point_lin read 25.7 us
         // against 14.7 us under rocprofv3); an empty launch takes that, the bracket of the real kernel then starts behind it like every other one
         if (h->profile && nP > 0 && !lin_done) hipLaunchKernelGGL(k_profile_pad, dim3(1), dim3(64), 0, st);
-        if (nP > 0 && !lin_done && !fuse_lin) point_lin(x, z.scal, nullptr);      // (lin_done: it ran speculatively behind the previous iteration, with this radius)
+        if (nP > 0 && !lin_done && !gp.fuse_lin) point_lin(x, z.scal, nullptr);      // (lin_done: it ran speculatively behind the previous iteration, with this radius)
         { const int rc = record_phase(1); if (rc) return rc; }
         if (!F.cs_task_cam.empty()) {
             const int ntasks = (int)F.cs_task_cam.size();
@@ -371,7 +327,7 @@ struct LmRun {
                    h->chunk_b0.p, h->chunk_b1.p, ntasks, h->batch_slot.p, h->pair_j.p, h->pair_j2.p, h->pair_p.p, h->scale_cam.p, h->Vs.p, loss, la, z.S_val,
                    occ3 ? DetZone{} : z.det);
         }
-        if (!F.gr_rec.empty() && !(fuse_lin && lin_done)) {          // (fused + lin_done: the whole assembly of this iteration ran speculatively behind the previous one)
+        if (!F.gr_rec.empty() && !(gp.fuse_lin && lin_done)) {          // (fused + lin_done: the whole assembly of this iteration ran speculatively behind the previous one)
             const int rc = launch_gram(x, z, nullptr); if (rc) return rc;
         }
         lin_done = false;
@@ -416,23 +372,11 @@ struct LmRun {
     bool may_speculate(bool with_cams) const { return spec_on && !with_cams && !(h->profile || O.verbose) && iteration < O.max_num_iterations; }
     // per point: back-substitution, candidate, model cost change, candidate cost.  res: the residual check of the reduced solve rides along
     void back_substitute(bool res) {
-        // the points of signature groups take k_gram_backsub (lane = observation, camera records in LDS); k_point_backsub keeps the others and
-        // the residual check's extra workgroup
-        // Its time follows the POINTS (8 lanes per point whatever K), k_point_backsub's the observations: measured (rounds 3-5, k_gram_backsub) 27.3 / 28.1 us
-        // at K = 6 / 8 against 23.4 / 31.7 (100k points) and 271 / 278 against 284 / 379 (1.5 M points).  Round 6, k_gram_backsub2: 195 us at 1.5 M points (K = 8),
-        // 21.1 against 23.0 us at config 2 (K = 6, four waves per task): on from 6 observations per point on average.
-        // SSFM_GRAM_BACKSUB=0 / 1 forces it off / on.
-        const bool grouped = !fused_publish() && !F.gr_rec.empty() && (gram_bs < 0 ? F.gram_obs >= 6 * F.gram_points : gram_bs != 0);
-        const bool all_grouped = grouped && F.gram_points == F.nP;               // then the residual check's workgroup rides with k_gram_backsub
-        if (grouped) gram_backsub(res && all_grouped);
-        if (all_grouped) return;
-        // EXPERIMENT, off (SSFM_BACKSUB_LPP=2): two lanes per point -- half the dependent camera gathers per lane, twice the waves.  Measured at config 2
-        // (scripts/lab/ab_lpp.sh, hipEvent averages): 25.1-25.3 us against 23.0-23.5 with one lane per point; 2.557 against 2.538-2.552 ms per solve
-        // r05ai: on LONG tracks it pays -- 300 cameras, tracks of 3 ... 14 (8.5 observations per point, 70 000 points = one wave per SIMD): 40.1 -> 33.0 us;
-        // tracks 3 ... 8 (5.5 per point): 26.7 -> 28.7.  Two lanes per point from 8.25 observations per point on.
-        const int bs_lpp_env = SSFM_LAB_KNOB("SSFM_BACKSUB_LPP", 0);
-        const int bs_lpp = bs_lpp_env > 0 ? bs_lpp_env : ((int64_t)4 * F.M > (int64_t)33 * F.nP ? 2 : 1);
-        point_backsub(bs_lpp == 2 ? 2 : 1, res, grouped ? h->pt_grouped.p : (const unsigned char*)nullptr, nullptr, nullptr);
+        // the points of signature groups take k_gram_backsub2 when the plan says so (gram_path.h: grouped); k_point_backsub keeps the others and, unless every point
+        // is grouped, the residual check's extra workgroup
+        if (gp.grouped) gram_backsub(res && gp.all_grouped);
+        if (gp.all_grouped) return;
+        point_backsub(gp.backsub_lpp, res, gp.grouped ? h->pt_grouped.p : (const unsigned char*)nullptr, nullptr, nullptr);
     }
     // candidate cameras + their rotation tables (with_cams; otherwise the solve's arrow kernel wrote them), the points' tail, the hand-over
     int enqueue_tail(bool with_cams) {
@@ -477,7 +421,7 @@ struct LmRun {
         if (!nc.in_finalize) SSFM_HIP_CHECK(ctx, hipMemsetAsync(nc.zone, 0, h->zone_len * sizeof(double), st));
         if (!spec_launched) return SSFM_OK;
         // x = this iteration's candidate, scalars into the next zone; [go, radius] from the device
-        if (fuse_lin) return launch_gram(c, zone(iteration + 1), (const double*)h->lmdev.p);
+        if (gp.fuse_lin) return launch_gram(c, zone(iteration + 1), (const double*)h->lmdev.p);
         point_lin(c, nc.zone, (const double*)h->lmdev.p);
         return SSFM_OK;
     }

@@ -1,4 +1,4 @@
-// csrc/gram_share.h: the share [s_begin, s_end) of a Gram task's cnt points that wave w of W takes (k_schur_gram with the task split over a workgroup).
+// csrc/gram_path.h, gram_share: the share [s_begin, s_end) of a Gram task's cnt points that wave w of W takes (k_schur_gram with the task split over a workgroup).
 // Stand-alone, under UBSan (tests/test_gram_split_cpu.py).  For cnt in 1..200 and W in 1..4:
 //   the shares are disjoint, in wave order, and cover [0, cnt);
 //   every share is made of whole sub-chunks of 8 points, except that the task's last sub-chunk may be partial;
@@ -6,10 +6,10 @@
 #include <cstdio>
 #include <vector>
 
-#include "../../spherical_sfm_amd/csrc/gram_share.h"
+#include "../../spherical_sfm_amd/csrc/gram_path.h"
 
 int main() {
-    using ssfm::GRAM_SHARE_SUB; using ssfm::gram_share;
+    constexpr int GRAM_SHARE_SUB = ssfm::GRAM_SUB_PTS; using ssfm::gram_share;
     int bad = 0, checked = 0;
     auto fail = [&](const char* what, int cnt, int W, int w, int b, int e) { if (bad++ < 20) std::printf("FAIL %s: cnt %d W %d w %d share [%d, %d)\n", what, cnt, W, w, b, e); };
     for (int cnt = 1; cnt <= 200; cnt++)

@@ -1,4 +1,4 @@
-"""csrc/gram_share.h: which sub-chunks of a Gram task each wave of its workgroup walks when k_schur_gram splits the task (ba_kernels.h: SPLIT).
+"""csrc/gram_path.h, gram_share: which sub-chunks of a Gram task each wave of its workgroup walks when k_schur_gram splits the task (ba_kernels.h: SPLIT).
 tests/native/gram_split_check.cpp, a stand-alone program under UBSan, checks for every task length 1..200 and 1..4 waves that the shares are disjoint and cover the
 task, are whole sub-chunks except the task's last, and are empty exactly when there are more waves than sub-chunks."""
 import os

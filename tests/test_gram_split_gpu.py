@@ -1,5 +1,5 @@
-"""A Gram task shared by the waves of a workgroup (ba_kernels.h: schur_gram_task<..., SPLIT = true>; ba_solver.hip: LmRun::gram_split, SSFM_GRAM_SPLIT): wave w walks
-its share of the task's sub-chunks (csrc/gram_share.h) through the point pass and the loop, the blocks and the cameras' vectors leave once per task as the sum of the
+"""A Gram task shared by the waves of a workgroup (ba_kernels.h: schur_gram_task<..., SPLIT = true>; gram_path.h: the waves per task of a launch, SSFM_GRAM_SPLIT): wave w walks
+its share of the task's sub-chunks (csrc/gram_path.h: gram_share) through the point pass and the loop, the blocks and the cameras' vectors leave once per task as the sum of the
 waves' LDS slices.  Same LM run as one wave per task (SSFM_GRAM_SPLIT=1, the kernel as it was) and as the oracle, on the problems of tests/test_gram_fused_gpu.py --
 every instantiation a problem can reach, the unfused three-tile class with k_point_lin in front included -- and on every shape of a share:
 
