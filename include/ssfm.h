@@ -782,6 +782,56 @@ int ssfm_build_tracks_device(ssfm_ctx* ctx, int32_t num_keyframes, const int32_t
                              int32_t* obs_cam, int32_t* obs_pt, int32_t* obs_feat, double* obs_xy);
 int ssfm_tracks_last_kernel_ms(ssfm_ctx* ctx, double* ms);
 
+/* ---- stereo panorama: make_stereo_panoramas (examples/stereo_panorama_tools.cpp:404-637) from poses, frames and optical flow -------------
+ * One cylindrical panorama per viewing angle phi.  Every output column is synthesised from one pair of consecutive keyframes k -> (k+1) mod n:
+ * a plane-induced column map into both frames (:69-106), optionally corrected by the optical flow between them (:135-188), two bilinear
+ * remaps and a blend.  The flow estimator stays outside, like SIFT: flows are an input; without them the call computes
+ * synthesize_column_linear (:108-133).  R is ROW-MAJOR [n*9] here (x_cam = R x_world + t), t [n*3]; the poses are expected levelled and scaled
+ * as estimate_plane leaves them (:276-358; csrc/shim/stereo_panorama_tools.h: level_keyframes).
+ *
+ * ssfm_pano_plan (host only, no GPU): the column jobs of :521-616.  A job is a (pair, thetanum, phinum) that passes the angle tests of
+ *   :582-592, listed pair-major, then thetanum, then phinum.  job_col = (thetanum + round(phi / theta_step)) mod pano_width, made non-negative;
+ *   job_ok = 1 when get_synthetic_column_maps would return true (XL(2) > 0 and XR(2) > 0 on every row); job_alpha = |angle_LD| / |angle_LR|;
+ *   job_consts [10 per job] = tan(phi), synth_R[9] row-major -- every transcendental of the stage is taken here, the kernel uses + - * / only.
+ *   owner [num_phi * pano_width]: the pair index of the ok job of the HIGHEST pair index that writes the column (the reference overwrites pair
+ *   by pair), -1 where none does.  *num_jobs: capacity of the job arrays in, number of jobs out; a capacity that is too small returns
+ *   SSFM_ERR_INVALID with the needed count in *num_jobs and the job arrays untouched (owner is still written).  Any output array may be NULL.
+ * ssfm_pano_synthesize: panoramas [num_phi][height][pano_width][3] bytes, every byte defined (columns nobody owns are 0).  frames [n] pointers to
+ *   height*width*3 bytes (channel order kept as is); flow_fwd [n] pointers to height*width*2 floats (dx, dy), entry k the flow of frame k ->
+ *   (k+1) mod n, flow_bwd entry k that of frame (k+1) mod n -> k; both arrays NULL = linear mode.  Entries of pairs that do not exist (the last
+ *   one of an open sweep) are not read.  Per pixel, the map in double in the order written in csrc/pano_host.h, rounded to float; then in fp32,
+ *   flow mode: xs_L = xL * 1 + ((xR - xL) - bilinear(flow_fwd, xL)) * (float)alpha, xs_R = xR * 1 + ((xL - xR) - bilinear(flow_bwd, xR)) *
+ *   (float)(1 - alpha); out = bilinear(frame_k, xs_L) * (float)(1 - alpha) + bilinear(frame_k+1, xs_R) * (float)alpha, rounded half to even and
+ *   clamped to 0..255 (NaN -> 0).  bilinear: x0 = floor(x), fx = x - x0, weights (1-fy)(1-fx), (1-fy)fx, fy(1-fx), fy fx formed first, the four
+ *   products summed left to right, a tap outside the image is 0, a non-finite coordinate or one beyond +-2^30 samples 0; with subpixel_bits = 5
+ *   a valid coordinate is first replaced by rint(x * 32) / 32 (the grid cv::remap interpolates on).  No multiply-add is fused.
+ *   on_device = 0: frames / flows / panoramas are host memory, staged pair slab by pair slab within max_slab_bytes (0 = 1 GiB; at least one pair)
+ *   through a pinned buffer of the context.  on_device = 1: the pointer arrays are host arrays of DEVICE pointers and panoramas is a device pointer;
+ *   nothing is copied, the work is queued on the context's stream and the call returns after it has finished.  owner_out (host, or NULL) receives
+ *   the owner map of the plan.
+ *   SSFM_ERR_INVALID before the device is touched: flow arrays given only one way, a null frame or flow pointer of an existing pair, pano_width < 2,
+ *   num_phi < 1, width or height < 1, a null context.
+ * ssfm_pano_last_kernel_ms: device time of the kernels of the context's last ssfm_pano_synthesize call (one hipEvent pair per slab). */
+typedef struct {
+    int32_t num_phi;             /* 9      (:485) */
+    int32_t is_loop;             /* 1: the last keyframe pairs with the first (:525-528) */
+    double  phi_step_deg;        /* 1.0    phi_i = (i - (num_phi-1)/2) * step; num_phi == 1 -> 0 (:486-494) */
+    double  depth;               /* 10.0   (:30) */
+    double  synth_radius;        /* 0.5    (:31) */
+    double  synth_focal_factor;  /* 1.2    (:32) */
+    int32_t subpixel_bits;       /* 0: sample at the float coordinate; 5: coordinates rounded to 1/32 px first */
+    int32_t on_device;           /* 0: frames / flows / panoramas are host pointers; 1: device pointers (no copies) */
+    int64_t max_slab_bytes;      /* 0 = default; device staging budget for frames + flows when on_device == 0 */
+} ssfm_pano_options;
+void ssfm_pano_default_options(ssfm_pano_options* opt);
+int ssfm_pano_plan(const ssfm_pano_options* opt, int32_t n, const double* R, const double* t, double focal, double cx, double cy,
+                   int32_t width, int32_t height, int32_t pano_width, int32_t* num_jobs, int32_t* job_pair, int32_t* job_theta, int32_t* job_phi,
+                   int32_t* job_col, uint8_t* job_ok, double* job_alpha, double* job_consts, int32_t* owner);
+int ssfm_pano_synthesize(ssfm_ctx* ctx, const ssfm_pano_options* opt, int32_t n, const double* R, const double* t, double focal, double cx, double cy,
+                         int32_t width, int32_t height, const uint8_t* const* frames, const float* const* flow_fwd, const float* const* flow_bwd,
+                         int32_t pano_width, uint8_t* panoramas, int32_t* owner_out);
+int ssfm_pano_last_kernel_ms(ssfm_ctx* ctx, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,11 @@ class AnmsOptionsC(C.Structure):
     _fields_ = [("force_j_chunks", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PanoOptionsC(C.Structure):
+    _fields_ = [("num_phi", C.c_int32), ("is_loop", C.c_int32), ("phi_step_deg", C.c_double), ("depth", C.c_double), ("synth_radius", C.c_double),
+                ("synth_focal_factor", C.c_double), ("subpixel_bits", C.c_int32), ("on_device", C.c_int32), ("max_slab_bytes", C.c_int64)]
+
+
 c_float_p = C.POINTER(C.c_float)
 
 
@@ -121,6 +126,7 @@ DECLARED_SYMBOLS = [
     "ssfm_focal_l1_default_options", "ssfm_focal_search_l1",
     "ssfm_anms_default_options", "ssfm_anms_batch", "ssfm_anms_batch_host", "ssfm_anms_last_kernel_ms",
     "ssfm_build_tracks_device", "ssfm_tracks_last_kernel_ms",
+    "ssfm_pano_default_options", "ssfm_pano_plan", "ssfm_pano_synthesize", "ssfm_pano_last_kernel_ms",
 ]
 
 
@@ -268,6 +274,14 @@ def lib():
                                            c_i32_p, c_i32_p, c_u8_p, c_i64_p, c_i32_p, c_i32_p, c_i32_p, c_double_p]
     L.ssfm_build_tracks_device.restype = C.c_int
     L.ssfm_tracks_last_kernel_ms.argtypes = [vp, c_double_p]; L.ssfm_tracks_last_kernel_ms.restype = C.c_int
+    L.ssfm_pano_default_options.argtypes = [C.POINTER(PanoOptionsC)]; L.ssfm_pano_default_options.restype = None
+    L.ssfm_pano_plan.argtypes = [C.POINTER(PanoOptionsC), C.c_int32, c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                                 c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_i32_p, c_u8_p, c_double_p, c_double_p, c_i32_p]
+    L.ssfm_pano_plan.restype = C.c_int
+    L.ssfm_pano_synthesize.argtypes = [vp, C.POINTER(PanoOptionsC), C.c_int32, c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                       C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_int32, vp, c_i32_p]
+    L.ssfm_pano_synthesize.restype = C.c_int
+    L.ssfm_pano_last_kernel_ms.argtypes = [vp, c_double_p]; L.ssfm_pano_last_kernel_ms.restype = C.c_int
     _LIB = L
     return L
 

@@ -47,6 +47,7 @@ extern "C" void ssfm_ctx_destroy(ssfm_ctx* ctx) {
     if (ctx->host_pub) (void)hipHostFree(ctx->host_pub);
     if (ctx->tracks_dev) (void)hipFree(ctx->tracks_dev);
     if (ctx->tracks_pin) (void)hipHostFree(ctx->tracks_pin);
+    if (ctx->pano_pin) (void)hipHostFree(ctx->pano_pin);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }

@@ -34,6 +34,8 @@ struct ssfm_ctx {
     double tracks_kernel_ms = 0.0;      // the same for the last ssfm_build_tracks_device call, ssfm_tracks_last_kernel_ms
     void* tracks_dev = nullptr; size_t tracks_dev_bytes = 0;     // device scratch of ssfm_build_tracks_device (tracks_device.hip), grow-only
     void* tracks_pin = nullptr; size_t tracks_pin_bytes = 0;     // its pinned staging, grow-only
+    double pano_kernel_ms = 0.0;        // device time of the kernels of the last ssfm_pano_synthesize call (an event pair per slab), ssfm_pano_last_kernel_ms
+    void* pano_pin = nullptr; size_t pano_pin_bytes = 0;         // pinned staging of its host-pointer mode (pano.hip), allocated once
 };
 
 namespace ssfm {
